@@ -20,6 +20,16 @@ piece ranges of the global batch (capnp_packed.shard.plan_shards), no
 collective on the data path (pieces are independent, Serialize.java:283-287).
 
 Run:  python bench.py [--gpus N --steps K --warmup W --config C]
+  A plain run sets up, warms up, times the K steps and prints the result
+  line, nothing else.
+  --dump-outputs DIR: after the timed steps, what the last step computed
+  (packed bytes, offsets, decoded words, statuses) goes to DIR/<name>.npy
+  (float32 / float64, a fixed seeded sample of the large arrays, under 64 MB
+  in all), so that two builds can be compared output for output.
+  --full: everything else the benchmark checks and measures, after the timed
+  steps: decoded == input, statuses, a sample of pieces against the host
+  oracle ("parity", --sample-check), the CPU baseline ("cpu_baseline",
+  --cpu-seconds, --no-cpu).
   --gpus N without a torch.distributed launcher starts N rank processes
   itself (before any GPU call); under torchrun WORLD_SIZE must equal N.
   --stub: CPU-only rehearsal of the multi-rank path (gloo, the oracle as
@@ -59,11 +69,15 @@ def parse(argv=None):
     ap.add_argument("--segments", type=int, default=None,
                     help="pieces per GPU (config 3: messages per GPU)")
     ap.add_argument("--seg-words", type=int, default=8192)
+    ap.add_argument("--full", action="store_true",
+                    help="also check parity (decoded == input, oracle sample) and time the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="time budget of each CPU-baseline sample (1 thread, then all threads)")
-    ap.add_argument("--no-cpu", action="store_true")
+                    help="--full: time budget of each CPU-baseline sample (1 thread, then all threads)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--sample-check", type=int, default=64,
-                    help="pieces re-packed on the host oracle and compared")
+                    help="--full: pieces re-packed on the host oracle and compared")
     ap.add_argument("--stub", action="store_true", help="CPU rehearsal (gloo, no GPU)")
     ap.add_argument("--same-device", action="store_true",
                     help="all ranks on cuda:0, gloo group (N > 1 rehearsal on one GPU)")
@@ -127,6 +141,54 @@ def rank_shard(args, lay, rank):
     return swo.astype(np.uint64), None
 
 
+# ---------------------------------------------------------------- --dump-outputs
+DUMP_TABLE_MAX = 1 << 19              # offsets / statuses: kept whole up to this many elements
+DUMP_CHUNKS, DUMP_CHUNK_BYTES = 768, 4096  # byte streams: this many runs of consecutive bytes
+
+
+def dump_indices(rng, tables, streams):
+    """Which elements --dump-outputs keeps, {name: sorted index array}: drawn
+    from `rng` in the order given, so the same arguments keep the same
+    elements.  tables {name: length}: whole up to DUMP_TABLE_MAX elements,
+    else that many distinct ones; streams {name: valid bytes}: whole up to
+    DUMP_CHUNKS * DUMP_CHUNK_BYTES bytes, else DUMP_CHUNKS runs of
+    DUMP_CHUNK_BYTES consecutive bytes."""
+    idx = {}
+    for name, n in tables.items():
+        idx[name] = np.arange(n, dtype=np.int64) if n <= DUMP_TABLE_MAX \
+            else np.sort(rng.choice(n, size=DUMP_TABLE_MAX, replace=False)).astype(np.int64)
+    for name, n in streams.items():
+        if n <= DUMP_CHUNKS * DUMP_CHUNK_BYTES:
+            idx[name] = np.arange(n, dtype=np.int64)
+        else:
+            starts = np.sort(rng.integers(0, n - DUMP_CHUNK_BYTES + 1, size=DUMP_CHUNKS, dtype=np.int64))
+            idx[name] = (starts[:, None] + np.arange(DUMP_CHUNK_BYTES, dtype=np.int64)).reshape(-1)
+    return idx
+
+
+def dump_outputs(dirpath, rank, world, tables, streams):
+    """Writes <name>.npy (rank r > 0 of several: rank<r>_<name>.npy) under
+    dirpath.  tables {name: 1-D integer array}; streams {name: (uint8 array,
+    valid bytes)}; numpy arrays or torch tensors.  Bytes and 32-bit values go
+    out as float32, 64-bit offsets as float64 (all exact)."""
+    out = Path(dirpath)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = dict(tables, **{k: v[0] for k, v in streams.items()})
+    idx = dump_indices(np.random.default_rng(SEED), {k: len(v) for k, v in tables.items()},
+                       {k: int(v[1]) for k, v in streams.items()})
+    total = 0
+    for name, a in arrays.items():
+        if isinstance(a, np.ndarray):
+            got = a[idx[name]]
+        else:
+            import torch
+            got = a[torch.from_numpy(idx[name]).to(a.device)].cpu().numpy()
+        got = got.astype(np.float64 if got.dtype.itemsize == 8 else np.float32)
+        total += got.nbytes
+        np.save(out / (f"rank{rank}_{name}.npy" if world > 1 and rank else f"{name}.npy"), got)
+    assert total <= 64 * 10 ** 6, total
+
+
 # ---------------------------------------------------------------- GPU rank
 def run_rank(args, rank, world, local):
     import torch
@@ -175,6 +237,9 @@ def run_rank(args, rank, world, local):
 
         def piece_range(i):
             return int(offs[i]), int(offs[i + 1])
+
+        def tables():
+            return {"packed_off": d_off, "piece_status": d_st}
     else:
         nm = len(mso) - 1
         d_mso = torch.from_numpy(mso.astype(np.int64)).to(dev)
@@ -206,6 +271,10 @@ def run_rank(args, rank, world, local):
             # segment i of message i // 4 is piece mso[m] + m + 1 + (i - mso[m])
             p = i + i // 4 + 1
             return int(offs[p]), int(offs[p + 1])
+
+        def tables():
+            return {"packed_off": d_off, "seg_word_off": d_swo_o, "seg_in_off": d_sio,
+                    "seg_status": d_sst, "msg_seg_off": d_mso_o, "msg_status": d_st}
     torch.cuda.synchronize(dev)
 
     def step(ev=None):
@@ -238,17 +307,23 @@ def run_rank(args, rank, world, local):
     dec_t = [e[1].elapsed_time(e[2]) for e in evs]
     enc_ms, dec_ms = float(np.median(enc_t)), float(np.median(dec_t))
 
-    # ---- parity: decoded == input, statuses, sample vs the host oracle ----
-    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-    ctx.count_mismatch(d_in, d_out, words, cnt, stream)
-    bad_status = int((d_st != 0).sum().item())
-    if mso is not None:
-        bad_status += int((d_sst != 0).sum().item()) + msg_fail[0]
-    mism = int(cnt.item())
-    offs = d_off.cpu().numpy().astype(np.uint64)
-    P = int(offs[-1])
+    P = int(d_off[-1].item())  # (the last offset is the packed total)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, tables(),
+                     {"packed": (d_pk, P), "decoded": (d_out.view(torch.uint8), U)})
+
+    # ---- --full, parity: decoded == input, statuses, sample vs the host oracle ----
+    mism = bad_status = 0
     sample_ok = None
-    if rank == 0 and args.sample_check > 0:
+    if args.full:
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        ctx.count_mismatch(d_in, d_out, words, cnt, stream)
+        bad_status = int((d_st != 0).sum().item())
+        if mso is not None:
+            bad_status += int((d_sst != 0).sum().item()) + msg_fail[0]
+        mism = int(cnt.item())
+        offs = d_off.cpu().numpy().astype(np.uint64)
+    if args.full and rank == 0 and args.sample_check > 0:
         sys.path.insert(0, str(REPO / "oracle"))
         import oracle  # checker only, after the timed region
         rng = np.random.default_rng(0)
@@ -333,7 +408,7 @@ def run_rank(args, rank, world, local):
     # (rank 0 at N = 1 only: at N > 1 the other ranks would wait on it and
     # the host cores are shared by all ranks)
     cpu = None
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         cpu = cpu_baseline(args, params)
 
     if mso is None:
@@ -385,7 +460,9 @@ def run_rank(args, rank, world, local):
             "note": "algorithmic U+P over the other stage's event time",
         },
         "roundtrip_roofline_frac": round(2 * (U + P) / ((enc_ms + dec_ms) * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-        "parity": {"mismatched_words_plus_bad_status": errors, "oracle_sample_equal": sample_ok},
+        # (parity and cpu_baseline: --full only, else null = not checked / not measured)
+        "parity": {"mismatched_words_plus_bad_status": errors, "oracle_sample_equal": sample_ok}
+        if args.full else None,
         "cpu_baseline": cpu,
     }
     if per_rank:
@@ -521,6 +598,9 @@ def run_stub(args, rank, world):
     if world > 1:
         dist.barrier()
     wall = time.perf_counter() - t0
+    if args.dump_outputs and args.steps:
+        dump_outputs(args.dump_outputs, rank, world, {"packed_off": off, "piece_status": st},
+                     {"packed": (pk, len(pk)), "decoded": (dec, len(dec))})
     U = float(8 * int(swo[-1]))
     vals = [wall, float(errs), U, float(len(swo) - 1)]
     if world > 1:

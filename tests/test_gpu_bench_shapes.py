@@ -157,7 +157,7 @@ def test_bench_two_ranks_same_device(config, segments):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "2", "--same-device",
                           "--config", str(config), "--segments", str(segments), "--steps", "3",
-                          "--warmup", "1", "--no-cpu", "--sample-check", "16"],
+                          "--warmup", "1", "--full", "--no-cpu", "--sample-check", "16"],
                          env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

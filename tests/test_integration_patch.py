@@ -2,10 +2,9 @@
 dispatch, Compression.GPU_PACKED, TestCase "gpu-packed", do_benchmarks.bash
 runs) is present, and the Java files it adds are the repository's current
 ones (regenerate with integration/make_patch.py after editing them)."""
+import json
 import re
 from pathlib import Path
-
-import pytest
 
 REPO = Path(__file__).resolve().parents[1]
 PATCH = REPO / "integration" / "capnproto-java.patch"
@@ -59,47 +58,63 @@ def test_patch_new_files_are_current():
         assert added == src.read_text().splitlines(), f"{rel} is stale: run integration/make_patch.py"
 
 
-REF = Path("/root/reference")
+OUTLINE = json.loads((Path(__file__).parent / "golden" / "serialize_packed_outline.json").read_text())
 
 
-def _methods(java: str):
-    """{signature: body} of every public static method (brace matched)."""
-    out = {}
-    for m in re.finditer(r"public static [^;{]*?\b(\w+)\(([^)]*)\)[^{;]*\{", java):
-        depth, i = 1, m.end()
-        while depth:
-            depth += {"{": 1, "}": -1}.get(java[i], 0)
-            i += 1
-        params = re.sub(r"\s+", " ", m.group(2)).strip()
-        out[f"{m.group(1)}({params})"] = java[m.end(): i - 1]
-    return out
+def _hunks(text, rel):
+    """The patch's hunks of file `rel` against the unpatched file's line
+    numbers: ({line: context text}, [(line the addition follows, added text)])."""
+    section = next(s for s in text.split("diff -ruN ") if s.startswith(f"a/{rel} "))
+    context, added, o = {}, [], None
+    for ln in section.splitlines()[3:]:
+        m = re.match(r"^@@ -(\d+),(\d+) \+(\d+),(\d+) @@", ln)
+        if m:
+            assert o is None or (o, n) == end, "hunk shorter or longer than its header says"
+            o, n = int(m.group(1)), int(m.group(3))
+            end = (o + int(m.group(2)), n + int(m.group(4)))
+        elif ln.startswith("+"):
+            added.append((o - 1, ln[1:]))
+            n += 1
+        else:
+            assert ln.startswith(" "), f"the dispatch only adds lines: {ln!r}"
+            context[o] = ln[1:]
+            o, n = o + 1, n + 1
+    assert (o, n) == end, "hunk shorter or longer than its header says"
+    return context, added
 
 
-def test_every_public_serialize_packed_method_dispatches(tmp_path):
+def test_every_public_serialize_packed_method_dispatches():
     """The patched SerializePacked.java (SerializePacked.java:35-134): each of
     its 12 public methods either hands the call to GpuDispatch or is a
     one-line overload (default ReaderOptions) of one that does -- no packed
-    read or write can reach the CPU codec without passing the dispatch."""
-    import shutil
-    import subprocess
-    if not REF.exists():
-        pytest.skip("needs the reference checkout (build container)")
-    rel = "runtime/src/main/java/org/capnproto/SerializePacked.java"
-    (tmp_path / rel).parent.mkdir(parents=True)
-    shutil.copy(REF / rel, tmp_path / rel)
-    sp_patch = PATCH.read_text().split("diff -ruN ")
-    hunk = "diff -ruN " + next(h for h in sp_patch if h.startswith(f"a/{rel} "))
-    r = subprocess.run(["patch", "-p1"], input=hunk, cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    ms = _methods((tmp_path / rel).read_text())
-    assert len(ms) == 12, sorted(ms)
-    direct = {k for k, body in ms.items() if "GpuDispatch" in body}
-    for k, body in ms.items():
-        if k in direct:
+    read or write can reach the CPU codec without passing the dispatch.
+    Where the unpatched file's methods stand is recorded in
+    tests/golden/serialize_packed_outline.json (names and line numbers); the
+    patch's own context lines must agree with it."""
+    context, added = _hunks(PATCH.read_text(), OUTLINE["source"])
+    ms = OUTLINE["methods"]
+    assert len(ms) == 12, ms
+    assert max(context) <= OUTLINE["lines"]
+    calls = [after for after, ln in added if "GpuDispatch" in ln]
+
+    def inside(m, after):
+        return m["open_line"] <= after < m["close_line"]
+
+    direct = [m for m in ms if any(inside(m, a) for a in calls)]
+    for a in calls:
+        assert any(inside(m, a) for m in ms), f"dispatch outside a public method, after line {a}"
+    for m in direct:
+        # the patch's context shows this method's declaration where the outline has it
+        decl = context.get(m["decl_line"], "")
+        assert "public static" in decl and f" {m['name']}(" in decl, (m, decl)
+        assert m["forwards_with_default_options_to"] is None
+    for m in ms:
+        if m in direct:
             continue
-        m = re.fullmatch(r"\s*return (\w+)\(input, ReaderOptions\.DEFAULT_READER_OPTIONS\);\s*", body)
-        assert m, f"{k} neither dispatches nor delegates: {body!r}"
-        target = [d for d in direct if d.startswith(m.group(1) + "(") and "ReaderOptions" in d
-                  and d.split(",")[0] == k.rstrip(")")]
+        k = f"{m['name']}({', '.join(m['params'])})"
+        assert m["forwards_with_default_options_to"], f"{k} neither dispatches nor delegates"
+        assert not any(inside(m, a) for a, _ in added), f"{k} no longer a one-line overload"
+        target = [d for d in direct if d["name"] == m["forwards_with_default_options_to"]
+                  and d["params"] == m["params"] + ["ReaderOptions"]]
         assert target, f"{k} delegates to an undispatched overload"
     assert len(direct) == 8
