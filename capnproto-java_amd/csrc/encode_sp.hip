@@ -27,6 +27,11 @@
 // is several units, each emitting its own bytes, the run state handed from
 // chunk to chunk (the state a chunk leaves is published for the next);
 // every unit is read once: traffic U + P for any mix of piece sizes.
+//
+// The kernel has two forms, SpDense and SpSparse below: what differs between
+// them is templated on the form (the ring and LDS layout, SpRegs, A1, B, the
+// kernel), everything else exists once.  The device gate picks the form
+// per batch (e4_gate_kernel, encode_v4.hip).
 
 #ifndef CPK_SP_WAVES
 #define CPK_SP_WAVES 4
@@ -35,45 +40,102 @@ constexpr int kSpWaves = CPK_SP_WAVES;
 constexpr int kSpThreads = 64 * kSpWaves;
 constexpr int kSpWS = 128 / kSpWaves;          // steps per wave
 constexpr int kSpCS = kSpWaves * kSpWS;        // steps per chunk (8192 words)
-#ifndef CPK_SP_RELOAD
-#define CPK_SP_RELOAD 0  // B reads the words again (L2) instead of keeping them in VGPRs from A1
+static_assert(kSpWaves <= 16 && kSpWS >= 4 && kSpWS <= 32 && kSpWS % 4 == 0, "wave count");
+
+// ---- the two forms ---------------------------------------------------------------
+// (the CPK_* macros: -D knobs for A/B builds of one form's value)
+#ifndef CPK_SP_RING_DENSE
+#define CPK_SP_RING_DENSE 11264
 #endif
-#ifndef CPK_SP_RING
-#define CPK_SP_RING 8192
+#ifndef CPK_SP_WPE
+#define CPK_SP_WPE 3
 #endif
-constexpr uint32_t kSpRing = CPK_SP_RING;      // output ring per wave (bytes)
-constexpr uint32_t kSpRingLines = kSpRing / 16;
-constexpr uint32_t kSpRing4 = kSpRing / 4;       // (dwords)
-static_assert(kSpRing % 16 == 0, "whole lines");
-// ring line of relative line i (the dense form's 11 KiB ring is no power of two)
-__device__ __forceinline__ uint32_t sp_rline(uint32_t i) {
-  return (kSpRingLines & (kSpRingLines - 1)) == 0 ? (i & (kSpRingLines - 1)) : (i % kSpRingLines);
-}
+#ifndef CPK_SPARSE_RING
+#define CPK_SPARSE_RING 4096
+#endif
+#ifndef CPK_SPARSE_WPE
+#define CPK_SPARSE_WPE 6
+#endif
+#ifndef CPK_SPARSE_A1G
+#define CPK_SPARSE_A1G 4
+#endif
+// The dense form: A1's words stay in 64 VGPRs for B.
+struct SpDense {
+  static constexpr bool kReload = false;
+  static constexpr bool kSkip = false;  // (its steps are rarely empty)
+  // head counts taken in every step: nearly every step has heads, no branch
+  // (config 2 encode -0.9 %)
+  static constexpr bool kHcAll = true;
+  // output ring per wave (bytes): 11 KiB, the most three workgroups per CU
+  // leave room for (round 4: config 2's ~7.7 KiB of output per wave
+  // overflowed 8 KiB rings often enough that waves waited for their offset a
+  // third of the time; 11 KiB: encode -11 %)
+  static constexpr uint32_t kRing = CPK_SP_RING_DENSE;
+  // workgroups per CU (the grid: kWpe x CUs; the registers must allow as many waves per SIMD)
+  static constexpr int kWpe = CPK_SP_WPE;
+};
+// The sparse form: B reads its words a second time (from L2: A1 read them
+// moments before) instead of holding them in 64 VGPRs, 4 KiB rings and 6
+// workgroups per CU.  Mostly-zero batches emit little, so each wave's output
+// fits its smaller ring and the extra occupancy pays (config 4 encode 3.12 ->
+// 2.89 ms per 131,072 pieces); on config 2 a wave's ~6 KiB of output
+// overflows the ring and it is 36 % slower, so the device gate takes it only
+// for batches whose sampled words are >= 85 % zero (e4_gate_kernel).
+struct SpSparse {
+  static constexpr bool kReload = true;
+  // a step of zero words and no head builds no strings, a pair of them is
+  // skipped whole (round 6, config 4 encode -1.1 %)
+  static constexpr bool kSkip = true;
+  // head counts only in steps with heads (+36 % without the branch)
+#ifdef CPK_SPARSE_HCALL
+  static constexpr bool kHcAll = true;
+#else
+  static constexpr bool kHcAll = false;
+#endif
+  static constexpr uint32_t kRing = CPK_SPARSE_RING;
+  static constexpr int kWpe = CPK_SPARSE_WPE;
+  static constexpr int kA1G = CPK_SPARSE_A1G;  // steps whose loads A1 keeps in flight per group
+};
+
 // overhang lines past the ring's end: a step's strings are laid out from the
 // ring position of its first byte without wrapping, so up to a step's 640
 // bytes + a string's spill land past the end (41 lines; the reader ORs line
 // r < 41 with overhang line r).  Round 5: no per-string wrap (config 2
 // encode -0.6 %, config 4 -1.8 %)
 constexpr uint32_t kSpOvLines = 41;
-constexpr uint32_t kSpRingStride = kSpRing + 16 * kSpOvLines;
-constexpr uint32_t kSpoLut = 0;                                      // u64[256]
-constexpr uint32_t kSpoMsk = 2048;                                   // u64[kSpCS][3]
-constexpr uint32_t kSpoRing = kSpoMsk + kSpCS * 24;                  // per wave
-constexpr uint32_t kSpoScr = kSpoRing + kSpWaves * kSpRingStride;    // u64[32]
-constexpr uint32_t kSpLds = kSpoScr + 32 * 8;  // 53,056 B (dense form, 11 KiB rings), 24,384 B (sparse form)
-static_assert(kSpWaves <= 16 && kSpWS >= 4 && kSpWS <= 32 && kSpWS % 4 == 0, "wave count");
-static_assert(kSpoRing % 16 == 0 && kSpoScr % 16 == 0, "LDS alignment");
+constexpr uint32_t kSpoLut = 0;                       // u64[256]
+constexpr uint32_t kSpoMsk = 2048;                    // u64[kSpCS][3]
+constexpr uint32_t kSpoRing = kSpoMsk + kSpCS * 24;   // per wave
+// a form's ring and LDS layout
+template <class F>
+struct SpLay {
+  static constexpr uint32_t kRingLines = F::kRing / 16;
+  static constexpr uint32_t kRing4 = F::kRing / 4;  // (dwords)
+  static constexpr uint32_t kRingStride = F::kRing + 16 * kSpOvLines;
+  static constexpr uint32_t kScr = kSpoRing + kSpWaves * kRingStride;  // u64[32]
+  static constexpr uint32_t kLds = kScr + 32 * 8;  // 53,056 B dense, 24,384 B sparse
+  // steps B lays out before the offset is needed (16 at 11 KiB, 6 at 4 KiB):
+  // every wave whose output fits its ring lays out all its steps before
+  // fetching the offset -- the look-back then runs last, when the pieces
+  // before have published (measured best)
+  static constexpr int kDefer = ((int)(F::kRing - 16) / 640) & ~1;
+  static_assert(F::kRing % 16 == 0, "whole lines");
+  static_assert(kSpoRing % 16 == 0 && kScr % 16 == 0, "LDS alignment");
+  static_assert(kDefer * 640 + 16 <= (int)F::kRing && kDefer % 2 == 0, "deferred steps must fit the ring");
+  static_assert(kLds * F::kWpe <= 160u * 1024u, "the workgroups per CU must fit its LDS");
+};
+// ring line of relative line i (the dense form's 11 KiB ring is no power of two)
+template <class F>
+__device__ __forceinline__ uint32_t sp_rline(uint32_t i) {
+  constexpr uint32_t n = SpLay<F>::kRingLines;
+  return (n & (n - 1)) == 0 ? (i & (n - 1)) : (i % n);
+}
 // scratch words: [0] ticket, [16..16 + waves) wave bytes, [5] piece offset,
 // [6..9] chunk exit state (two parities x {zl, dlo | hd << 1}), [11] the piece
 // (+ 1) whose offset [5] holds
 // Steps are scheduled one at a time: hoisting later steps' LUT reads and
 // lane reads ahead would keep them all live at once (VGPR spills).
 #define CPK_SP_STEP_FENCE() __builtin_amdgcn_sched_barrier(0)
-#ifndef CPK_SP_WPE
-#define CPK_SP_WPE 3  // waves per SIMD the registers must allow (3 workgroups per CU)
-#endif
-constexpr int kSpWpe = CPK_SP_WPE;  // workgroups per CU (the grid: kSpWpe x CUs)
-static_assert(kSpLds * kSpWpe <= 160u * 1024u, "the workgroups per CU must fit its LDS");
 
 // status word per piece: [63:62] flag (1 aggregate, 2 inclusive prefix),
 // [61:46] launch epoch, [45:0] value (a relaxed 8-byte agent-scope granule:
@@ -86,11 +148,7 @@ __device__ __forceinline__ uint32_t sp_flag(uint64_t w, uint32_t ep) {
   return (uint32_t)((w >> 46) & 0xffffu) == (ep & 0xffffu) ? (uint32_t)(w >> 62) : 0u;
 }
 
-// (SpSt and sp_roles: sp_roles.hip, included by encode_v4.hip; the sparse
-// form's namespace includes its own copy, so its calls do not meet cpk's)
-#if CPK_SP_OWN_ROLES
-#include "sp_roles.hip"
-#endif
+// (SpSt and sp_roles: sp_roles.hip, included by encode_v4.hip)
 
 __device__ __forceinline__ uint64_t sp_ld(const uint64_t *p) { return sp_uni(*p); }
 
@@ -176,18 +234,21 @@ __device__ uint32_t sp_cont(const uint64_t *msk, int s, int cs, int cls, uint32_
   return min(r, 256u);
 }
 
-#ifndef CPK_SP_A1G
-#define CPK_SP_A1G 8  // (reload form) steps whose loads A1 keeps in flight per group
-#endif
-struct SpRegs {
-#if !CPK_SP_RELOAD
-  uint64_t v[kSpWS];       // the words, step j in v[j]
-#endif
+// What a wave keeps of its steps from A1 to B, whatever the form
+struct SpStash {
   uint32_t mp[kSpWS / 4];  // tags, four per register
   uint32_t zl, zh, dll, dlh, dl_, dh_;                 // A1 stash: Z, DL, D (lane = step)
   uint32_t oml, omh, ohl, ohh, oel, oeh;               // A2 stash: Mem, HC, E
   uint32_t ox;                                         //   X: words past the step to the next run end
 };
+// ... and the words themselves, unless B reads them again (the words first: as they always lay)
+struct SpWords {
+  uint64_t v[kSpWS];  // step j in v[j]
+};
+template <class F, bool kReload = F::kReload>
+struct SpRegs : SpWords, SpStash {};
+template <class F>
+struct SpRegs<F, true> : SpStash {};
 
 // A1: the wave's cnt steps at src (wrem piece words from src on); returns
 // this lane's nonzero-byte count
@@ -195,13 +256,12 @@ struct SpRegs {
 // step waits only for its own load (vmcnt(kSpWS - 1 - j)); with the per-step
 // branches of the general form the compiler waits for all of them at the
 // first step
-#if CPK_SP_RELOAD
-// reload form: the words are not kept for B; loads in groups of CPK_SP_A1G
+// reload form: the words are not kept for B; loads in groups of F::kA1G
 // steps, the next group's in flight while a group's tags are taken
-template <bool kFull>
-__device__ __forceinline__ uint32_t sp_a1(SpRegs &R, const uint64_t *__restrict__ src, uint32_t wrem,
+template <class F, bool kFull>
+__device__ __forceinline__ uint32_t sp_a1(SpRegs<F, true> &R, const uint64_t *__restrict__ src, uint32_t wrem,
                                           int cnt, int lane) {
-  constexpr int G = CPK_SP_A1G;
+  constexpr int G = F::kA1G;
   static_assert(kSpWS % G == 0, "A1 groups");
   uint64_t v[2][G];
   auto ld = [&](int j) __attribute__((always_inline)) -> uint64_t {
@@ -243,9 +303,9 @@ __device__ __forceinline__ uint32_t sp_a1(SpRegs &R, const uint64_t *__restrict_
   }
   return acc;
 }
-#else
-template <bool kFull>
-__device__ __forceinline__ uint32_t sp_a1(SpRegs &R, const uint64_t *__restrict__ src, uint32_t wrem,
+// the words kept in R.v, every load in flight at once
+template <class F, bool kFull>
+__device__ __forceinline__ uint32_t sp_a1(SpRegs<F, false> &R, const uint64_t *__restrict__ src, uint32_t wrem,
                                           int cnt, int lane) {
   // loads clamped to the piece, not predicated: step j's lanes read
   // min(lane, last valid lane of the step) (one lane register for all steps)
@@ -279,10 +339,9 @@ __device__ __forceinline__ uint32_t sp_a1(SpRegs &R, const uint64_t *__restrict_
   }
   return acc;
 }
-#endif
 
 // the wave's masks to LDS (lane j = step sa + j)
-__device__ __forceinline__ void sp_put_masks(const SpRegs &R, uint64_t *msk, int sa, int cnt, int lane) {
+__device__ __forceinline__ void sp_put_masks(const SpStash &R, uint64_t *msk, int sa, int cnt, int lane) {
   if (lane < cnt) {
     uint64_t *m = msk + 3 * (sa + lane);
     m[0] = (uint64_t)R.zl | ((uint64_t)R.zh << 32);
@@ -299,7 +358,7 @@ __device__ __forceinline__ void sp_put_masks(const SpRegs &R, uint64_t *msk, int
 // their nonzero bytes.  nz0 / ndl0: bit 0 of the step after the wave's last.
 // Used when a D/L stretch longer than 192 words enters a step (a literal run
 // may end inside it); sp_a2p otherwise.
-__device__ __forceinline__ uint32_t sp_a2_seq(SpRegs &R, int cnt, uint32_t wrem, SpSt st, uint32_t nz0, uint32_t ndl0) {
+__device__ __forceinline__ uint32_t sp_a2_seq(SpStash &R, int cnt, uint32_t wrem, SpSt st, uint32_t nz0, uint32_t ndl0) {
   uint32_t bytes = 0;
   for (int j = 0; j < cnt; ++j) {
     const uint64_t Z = sp_rl(R.zl, R.zh, j), DL = sp_rl(R.dll, R.dlh, j), D = sp_rl(R.dl_, R.dh_, j);
@@ -337,7 +396,7 @@ __device__ __forceinline__ uint32_t sp_from(uint32_t v, int src) {
 // over the steps.  Exact while every literal run that enters a step covers
 // it to its end, i.e. no D/L stretch longer than 192 words enters a step:
 // returns false (nothing written) when one does.  Same stash as sp_a2_seq.
-__device__ __forceinline__ bool sp_a2p(SpRegs &R, int cnt, uint32_t wrem, SpSt st, uint32_t nz0,
+__device__ __forceinline__ bool sp_a2p(SpStash &R, int cnt, uint32_t wrem, SpSt st, uint32_t nz0,
                                        uint32_t ndl0, int lane, uint32_t &bytes) {
   const bool act = lane < cnt;
   const uint64_t Z = act ? ((uint64_t)R.zl | ((uint64_t)R.zh << 32)) : 0ull;
@@ -408,7 +467,7 @@ __device__ __forceinline__ bool sp_a2p(SpRegs &R, int cnt, uint32_t wrem, SpSt s
 // X per step (lane = step): words past the step's end to the first run end
 // after it (a head's count reaches that far), from the next step with a run
 // end; past the wave's last step, Xlast.  At most 256.
-__device__ __forceinline__ void sp_xs(SpRegs &R, int cnt, uint32_t Xlast, int lane) {
+__device__ __forceinline__ void sp_xs(SpStash &R, int cnt, uint32_t Xlast, int lane) {
   const bool act = lane < cnt;
   const uint64_t E = (uint64_t)R.oel | ((uint64_t)R.oeh << 32);
   const uint64_t en = __ballot(act && E != 0);
@@ -422,19 +481,20 @@ __device__ __forceinline__ void sp_xs(SpRegs &R, int cnt, uint32_t Xlast, int la
 
 // ---- the output ring -----------------------------------------------------------
 // A wave lays its strings out relative to its first output byte: relative
-// line i (bytes [16 i, 16 i + 16)) lives at ring line i % kSpRingLines; a
+// line i (bytes [16 i, 16 i + 16)) lives at ring line i % kRingLines; a
 // string crossing the ring's end spills into the overhang line, which belongs
 // to ring line 0.  Its offset g0 in the output may not be known yet (the
 // look-back); once it is, relative line t goes to output bytes
 // [g0 + 16 t, g0 + 16 t + 16) as one 16-byte store at whatever alignment g0
 // has (round 5: no longer shifted onto the 16-byte-aligned output lines,
 // which took two ring lines and four v_alignbyte per line; encode -8 %).
+template <class F>
 __device__ __forceinline__ uint4 sp_ring_line(const uint32_t *ring, uint32_t i) {
   const uint4 *rl = reinterpret_cast<const uint4 *>(ring);
-  const uint32_t r = sp_rline(i);
+  const uint32_t r = sp_rline<F>(i);
   uint4 v = rl[r];
   if (r < kSpOvLines) {
-    const uint4 o = rl[kSpRingLines + r];
+    const uint4 o = rl[SpLay<F>::kRingLines + r];
     v.x |= o.x;
     v.y |= o.y;
     v.z |= o.z;
@@ -442,50 +502,46 @@ __device__ __forceinline__ uint4 sp_ring_line(const uint32_t *ring, uint32_t i) 
   }
   return v;
 }
+template <class F>
 __device__ __forceinline__ void sp_ring_clear(uint32_t *ring, uint32_t i) {
   uint4 *rl = reinterpret_cast<uint4 *>(ring);
-  const uint32_t r = sp_rline(i);
+  const uint32_t r = sp_rline<F>(i);
   rl[r] = make_uint4(0u, 0u, 0u, 0u);
-  if (r < kSpOvLines) rl[kSpRingLines + r] = make_uint4(0u, 0u, 0u, 0u);
+  if (r < kSpOvLines) rl[SpLay<F>::kRingLines + r] = make_uint4(0u, 0u, 0u, 0u);
 }
 // relative lines [ft, upto) to the output at g0 + 16 t: 16-byte stores at
 // any byte alignment (every byte of the wave's output is stored by exactly
 // one lane, no line is assembled from two), each line cleared once stored
 typedef unsigned int sp_u32x4u __attribute__((ext_vector_type(4), aligned(1)));
+template <class F>
 __device__ __forceinline__ void sp_flush_rel(uint8_t *out, uint32_t *ring, uint64_t g0, uint32_t &ft,
                                              uint32_t upto, int lane, uint64_t ocap) {
   for (uint32_t t0 = ft; t0 < upto; t0 += 64) {
     const uint32_t t = t0 + (uint32_t)lane;
     if (t < upto) {
-      const uint4 v = sp_ring_line(ring, t);
+      const uint4 v = sp_ring_line<F>(ring, t);
       const uint64_t a = g0 + 16ull * t;
       if (a + 16 <= ocap) {
         const sp_u32x4u w = {v.x, v.y, v.z, v.w};
         __builtin_nontemporal_store(w, reinterpret_cast<sp_u32x4u *>(out + a));
       }
-      sp_ring_clear(ring, t);
+      sp_ring_clear<F>(ring, t);
     }
   }
   ft = upto;
 }
 
 // B: the wave's strings, laid out relative to its first output byte.  Its
-// offset is given (known) or fetched once kSpDefer steps are in the ring
+// offset is given (known) or fetched once kDefer steps are in the ring
 // (getbase: wave 0 runs the piece's look-back meanwhile -- the other waves
 // have had that many steps of work before they wait for it).
-// steps laid out before the offset is needed (12 at 8 KiB)
-constexpr int kSpDefer = (((int)(kSpRing - 16) / 640) & ~1);
-// (every wave whose output fits its ring lays out all its steps before
-// fetching the offset: the look-back then runs last, when the pieces before
-// have published -- measured best)
-static_assert(kSpDefer * 640 + 16 <= (int)kSpRing && kSpDefer % 2 == 0, "deferred steps must fit the ring");
-template <class GetBase>
-__device__ __forceinline__ void sp_b(SpRegs &R, int cnt, const uint64_t *lut, uint32_t *ring, uint8_t *out,
+template <class F, class GetBase>
+__device__ __forceinline__ void sp_b(SpRegs<F> &R, int cnt, const uint64_t *lut, uint32_t *ring, uint8_t *out,
                                      bool known, bool fits, uint64_t g0, int lane, uint64_t ocap,
                                      const uint64_t *__restrict__ src, uint32_t wrem, GetBase getbase) {
-#if CPK_SP_RELOAD
-  // the words again (read by A1 moments ago: L2), 2 pairs ahead
-  uint64_t pv[kSpWS];
+  constexpr int kDefer = SpLay<F>::kDefer;
+  // (reload form) the words again (read by A1 moments ago: L2), 2 pairs ahead
+  uint64_t pv[F::kReload ? kSpWS : 1];
   // only the lanes whose word is nonzero load it (a zero word's string
   // needs no bytes): a line of zero words is not fetched again at all
   auto ldw = [&](int j) __attribute__((always_inline)) {
@@ -494,9 +550,10 @@ __device__ __forceinline__ void sp_b(SpRegs &R, int cnt, const uint64_t *lut, ui
       pv[j] = m ? ld_stream(&(src + j * 64)[min((uint32_t)lane, min(wrem - 1 - 64u * j, 63u))]) : 0ull;
     }
   };
+  if constexpr (F::kReload) {
 #pragma unroll
-  for (int j = 0; j < 2 * 2; ++j) ldw(j);
-#endif
+    for (int j = 0; j < 2 * 2; ++j) ldw(j);
+  }
   uint32_t rel = 0, ft = 0;
   // the output offset is wave-uniform: say so (readfirstlane), or the flush
   // condition and the line shift's switch on g0 & 15 compile to exec-masked
@@ -509,11 +566,10 @@ __device__ __forceinline__ void sp_b(SpRegs &R, int cnt, const uint64_t *lut, ui
     const uint64_t Mem = sp_rl(R.oml, R.omh, j);
     const uint64_t HC = sp_rl(R.ohl, R.ohh, j);
     const uint32_t m = (R.mp[j >> 2] >> (8 * (j & 3))) & 0xffu;
-#if CPK_SP_RELOAD
-    const uint32_t lo = (uint32_t)pv[j], hi = (uint32_t)(pv[j] >> 32);
-#else
-    const uint32_t lo = (uint32_t)R.v[j], hi = (uint32_t)(R.v[j] >> 32);
-#endif
+    uint64_t x;
+    if constexpr (F::kReload) x = pv[j];
+    else x = R.v[j];
+    const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
     const uint64_t sel = lut[m];
     const uint32_t c0 = __builtin_amdgcn_perm(hi, lo, (uint32_t)sel);
     const uint32_t c1 = __builtin_amdgcn_perm(hi, lo, (uint32_t)(sel >> 32));
@@ -522,13 +578,7 @@ __device__ __forceinline__ void sp_b(SpRegs &R, int cnt, const uint64_t *lut, ui
     // selects below take scalar mask algebra instead of per-lane selects)
     const uint64_t ZW = __ballot(zw);
     uint32_t cz = 0, cd = 0;
-#if CPK_SP_HCALL
-    // (the dense form: nearly every step has heads, no branch -- config 2
-    // encode -0.9 %; the sparse form keeps it, +36 % without)
-#else
-    if (HC)
-#endif
-    {
+    if (F::kHcAll || HC) {
       // a head's count: words to its run's end, at most 255 (:119-131, :143-164)
       const uint32_t X = (uint32_t)__builtin_amdgcn_readlane((int)R.ox, j);
       const uint64_t E = sp_rl(R.oel, R.oeh, j);
@@ -580,30 +630,25 @@ __device__ __forceinline__ void sp_b(SpRegs &R, int cnt, const uint64_t *lut, ui
   // steps j and j + 1 (when j + 1 < cnt): both byte counts in one wave scan
   // (16-bit halves: a step's strings total at most 640 bytes)
   auto step = [&](const int j) __attribute__((always_inline)) {
-#if CPK_SP_RELOAD
-    ldw(j + 2 * 2);
-    ldw(j + 2 * 2 + 1);
-#endif
-#if CPK_SP_SKIP
-    // (the sparse form: a step of zero words and no head -- inside a zero
-    // run -- has no bytes: its strings are not built, and a pair of them is
-    // skipped whole)
-    auto empty = [&](const int k) __attribute__((always_inline)) {
-      const uint32_t m = (R.mp[k >> 2] >> (8 * (k & 3))) & 0xffu;
-      return k >= cnt || (__ballot(m != 0u) == 0ull && sp_rl(R.ohl, R.ohh, k) == 0ull);
-    };
-    const bool ea = empty(j), eb = empty(j + 1);
-    if (!(ea && eb))
-#endif
-    {
+    if constexpr (F::kReload) {
+      ldw(j + 2 * 2);
+      ldw(j + 2 * 2 + 1);
+    }
+    // steps without strings: past the wave's last, or (kSkip) one of zero
+    // words and no head -- inside a zero run; a pair of them is skipped whole
+    bool ea = false, eb = false;
+    if constexpr (F::kSkip) {
+      auto empty = [&](const int k) __attribute__((always_inline)) {
+        const uint32_t m = (R.mp[k >> 2] >> (8 * (k & 3))) & 0xffu;
+        return k >= cnt || (__ballot(m != 0u) == 0ull && sp_rl(R.ohl, R.ohh, k) == 0ull);
+      };
+      ea = empty(j);
+      eb = empty(j + 1);
+    }
+    if (F::kSkip ? !(ea && eb) : true) {
       uint32_t a0 = 0, a1 = 0, a2 = 0, na = 0, b0 = 0, b1 = 0, b2 = 0, nb2 = 0;
-#if CPK_SP_SKIP
-      if (!ea) strings(j, a0, a1, a2, na);
-      if (!eb) strings(j + 1, b0, b1, b2, nb2);
-#else
-      strings(j, a0, a1, a2, na);
-      if (j + 1 < cnt) strings(j + 1, b0, b1, b2, nb2);
-#endif
+      if (F::kSkip ? !ea : true) strings(j, a0, a1, a2, na);
+      if (F::kSkip ? !eb : j + 1 < cnt) strings(j + 1, b0, b1, b2, nb2);
       const uint32_t pk = na | (nb2 << 16);
       const uint32_t incl = (uint32_t)wave_incl_add((int)pk);
       const uint32_t stot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
@@ -612,8 +657,8 @@ __device__ __forceinline__ void sp_b(SpRegs &R, int cnt, const uint64_t *lut, ui
         {
           // (per step, scalar: its first dword's ring position minus that dword)
           const uint32_t qa = rel >> 2, relb = rel + ta, qb = relb >> 2;
-          put(rel + (incl & 0xffffu) - na, a0, a1, a2, na, qa % kSpRing4 - qa);
-          put(relb + (incl >> 16) - nb2, b0, b1, b2, nb2, qb % kSpRing4 - qb);
+          put(rel + (incl & 0xffffu) - na, a0, a1, a2, na, qa % SpLay<F>::kRing4 - qa);
+          put(relb + (incl >> 16) - nb2, b0, b1, b2, nb2, qb % SpLay<F>::kRing4 - qb);
         }
         rel += ta + (stot >> 16);
         // complete lines leave 64 at a time (one full-wave store)
@@ -621,7 +666,7 @@ __device__ __forceinline__ void sp_b(SpRegs &R, int cnt, const uint64_t *lut, ui
           const uint32_t done = rel >> 4;
           if (done - ft >= 64u) {
             wave_lds_order();
-            sp_flush_rel(out, ring, g0, ft, ft + 64, lane, ocap);
+            sp_flush_rel<F>(out, ring, g0, ft, ft + 64, lane, ocap);
             wave_lds_order();
           }
         }
@@ -632,30 +677,30 @@ __device__ __forceinline__ void sp_b(SpRegs &R, int cnt, const uint64_t *lut, ui
   };
   // (two fully unrolled loops around the one place the offset may be fetched)
 #pragma unroll
-  for (int j = 0; j < kSpDefer; j += 2)
+  for (int j = 0; j < kDefer; j += 2)
     if (j < cnt) step(j);
-  if (!known && !fits && cnt > kSpDefer) {
+  if (!known && !fits && cnt > kDefer) {
     g0 = getbase();
     g0 = sp_uni(g0);
     known = true;
   }
 #pragma unroll
-  for (int j = kSpDefer; j < kSpWS; j += 2)
+  for (int j = kDefer; j < kSpWS; j += 2)
     if (j < cnt) step(j);
   if (!known) g0 = getbase();
   g0 = sp_uni(g0);
   wave_lds_order();
   const uint32_t done = rel >> 4, rem = rel & 15;
-  sp_flush_rel(out, ring, g0, ft, done, lane, ocap);
+  sp_flush_rel<F>(out, ring, g0, ft, done, lane, ocap);
   if (rem) {
     // the last, partial line: its bytes one per lane
-    const uint4 v = sp_ring_line(ring, done);
+    const uint4 v = sp_ring_line<F>(ring, done);
     const uint64_t a = g0 + 16ull * done + (uint32_t)lane;
     if ((uint32_t)lane < rem && a < ocap) {
       const uint32_t d = (lane & 8) ? ((lane & 4) ? v.w : v.z) : ((lane & 4) ? v.y : v.x);
       out[a] = (uint8_t)(d >> (8 * (lane & 3)));
     }
-    if (lane == 0) sp_ring_clear(ring, done);
+    if (lane == 0) sp_ring_clear<F>(ring, done);
   }
   wave_lds_order();
 }
@@ -766,7 +811,8 @@ __device__ __forceinline__ SpSt sp_unpack_state(uint64_t v) {
 // predecessor chunk of the piece published (prev, epoch-tagged, flag 2),
 // waited for once this chunk's masks are in LDS; the state leaving it is
 // published at next when the piece continues.
-__device__ __forceinline__ uint64_t sp_chunk(SpRegs &R, const uint64_t *__restrict__ pw, uint32_t W,
+template <class F>
+__device__ __forceinline__ uint64_t sp_chunk(SpRegs<F> &R, const uint64_t *__restrict__ pw, uint32_t W,
                                              uint32_t c, uint64_t *msk, uint64_t *scr, uint64_t *prev,
                                              uint64_t *next, uint32_t ep, uint32_t *err, int w, int lane,
                                              int &cnt, uint32_t &Xlast, uint64_t &wbefore,
@@ -786,9 +832,9 @@ __device__ __forceinline__ uint64_t sp_chunk(SpRegs &R, const uint64_t *__restri
   wrem_o = wrem;
   uint32_t acc = 0;
   if (cnt) {
-    if (cnt == kSpWS && wrem >= 64u * kSpWS) acc = sp_a1<true>(R, pw + wfirst, wrem, cnt, lane);
+    if (cnt == kSpWS && wrem >= 64u * kSpWS) acc = sp_a1<F, true>(R, pw + wfirst, wrem, cnt, lane);
     else
-      acc = sp_a1<false>(R, pw + wfirst, wrem, cnt, lane);
+      acc = sp_a1<F, false>(R, pw + wfirst, wrem, cnt, lane);
     sp_put_masks(R, msk, sa, cnt, lane);
   }
   SP_A1_STAMP
@@ -888,14 +934,23 @@ __device__ __forceinline__ uint64_t sp_chunk(SpRegs &R, const uint64_t *__restri
 // piece takes the run state its predecessor leaves (ustate[u - 1]), so a
 // large piece is encoded by many workgroups at once and read once (U + P),
 // and no piece waits for a large one before it to be emitted.
-template <bool kMsg>
-__global__ __launch_bounds__(kSpThreads, CPK_SP_WPE) void sp_encode_kernel(
+// The kernel of a form is this template with the form as its second
+// argument: cpk::sp_encode_kernel<kMsg> is the dense form,
+// cpk::sp_encode_kernel<false, SpSparse> the sparse one (message batches take
+// the dense form: the sparse form's message variant is never instantiated).
+// The body is the kernel itself, not a function under an entry point per
+// form: a function level here is optimized once on its own and again inside
+// its caller, and the unit loop then comes out differently (dense form: one
+// VGPR and 2-5 SGPR spills more).
+template <bool kMsg, class F = SpDense>
+__global__ __launch_bounds__(kSpThreads, F::kWpe) void sp_encode_kernel(
     const uint64_t *__restrict__ in, const uint64_t *__restrict__ swo,
     const uint64_t *__restrict__ pdesc, const uint64_t *__restrict__ tin, uint32_t n,
     uint8_t *__restrict__ out, uint64_t *__restrict__ out_off, uint64_t *status, uint32_t ep,
     uint32_t *ticket, const uint64_t *__restrict__ utab, const uint64_t *__restrict__ nunits,
     uint64_t *ustate, uint64_t hint, uint32_t *err, const uint64_t *ocapp, const uint32_t *pick, uint32_t mine,
     uint64_t ucap) {
+  using L = SpLay<F>;
   // (pick: the device gate's choice between this form and the other one)
   if (pick && (uint32_t)__builtin_amdgcn_readfirstlane((int)*pick) != mine) return;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -906,14 +961,14 @@ __global__ __launch_bounds__(kSpThreads, CPK_SP_WPE) void sp_encode_kernel(
   const uint64_t ocap = min(kMsg ? *ocapp : 9 * (swo[n] - swo[0]) + n + 16, ucap);
   uint64_t *lut = reinterpret_cast<uint64_t *>(smem + kSpoLut);
   uint64_t *msk = reinterpret_cast<uint64_t *>(smem + kSpoMsk);
-  uint64_t *scr = reinterpret_cast<uint64_t *>(smem + kSpoScr);
+  uint64_t *scr = reinterpret_cast<uint64_t *>(smem + L::kScr);
   const int lane0 = lane_id();
   const int w = __builtin_amdgcn_readfirstlane(wave_id());
-  uint32_t *ring = reinterpret_cast<uint32_t *>(smem + kSpoRing + w * kSpRingStride);
+  uint32_t *ring = reinterpret_cast<uint32_t *>(smem + kSpoRing + w * L::kRingStride);
   fill_luts(lut, false);
-  for (uint32_t i = lane0; i < kSpRingStride / 16; i += 64)
+  for (uint32_t i = lane0; i < L::kRingStride / 16; i += 64)
     reinterpret_cast<uint4 *>(ring)[i] = make_uint4(0u, 0u, 0u, 0u);
-  SpRegs R;
+  SpRegs<F> R;
   R.zl = R.zh = R.dll = R.dlh = R.dl_ = R.dh_ = 0;
   R.oml = R.omh = R.ohl = R.ohh = R.oel = R.oeh = 0;
   if (threadIdx.x == 0) scr[11] = 0;  // (LDS holds whatever the last kernel left)
@@ -957,9 +1012,9 @@ __global__ __launch_bounds__(kSpThreads, CPK_SP_WPE) void sp_encode_kernel(
     uint64_t wbefore = 0, wmine = 0;
     const uint64_t *wsrc = pw;
     uint32_t wrem = 0;
-    const uint64_t ct = sp_chunk(R, pw, W, c, msk, scr, c ? ustate + (t - 1) : nullptr,
-                                 lastc ? nullptr : ustate + t, ep, err, w, lane, cnt, Xlast, wbefore,
-                                 wmine, wsrc, wrem SP_A1_ARGS);
+    const uint64_t ct = sp_chunk<F>(R, pw, W, c, msk, scr, c ? ustate + (t - 1) : nullptr,
+                                    lastc ? nullptr : ustate + t, ep, err, w, lane, cnt, Xlast, wbefore,
+                                    wmine, wsrc, wrem SP_A1_ARGS);
     WPH(1)
     if (w == 0 && lane == 0) {
       // the unit's size, published before its strings are laid out: the
@@ -968,7 +1023,7 @@ __global__ __launch_bounds__(kSpThreads, CPK_SP_WPE) void sp_encode_kernel(
     }
     WPH(2)
     // the offset: the look-back (wave 0) runs once the waves have laid out
-    // kSpDefer steps (or all of them, when they fit the ring)
+    // L::kDefer steps (or all of them, when they fit the ring)
     auto getoff = [&]() {
       const uint64_t excl = sp_lookback(status, t, ct, ep, err, lane);
       // (a unit whose bytes pass the caller's capacity: reported; its lines
@@ -995,8 +1050,8 @@ __global__ __launch_bounds__(kSpThreads, CPK_SP_WPE) void sp_encode_kernel(
         WPH(6)
         return sp_ld(&scr[5]) + wbefore;
       };
-      sp_b(R, cnt, lut, ring, out, false, wmine + 16 <= kSpRing, wbefore, lane, ocap,
-           wsrc, wrem, getbase);
+      sp_b<F>(R, cnt, lut, ring, out, false, wmine + 16 <= F::kRing, wbefore, lane, ocap,
+              wsrc, wrem, getbase);
     } else if (w == 0) {
       getoff();  // wave 0 runs the look-back even without steps (an empty piece)
     }

@@ -5,6 +5,8 @@
 // pass's per-unit algebra (A1 tags / ballots, A2 roles, B strings),
 // PackedOutputStream.java:35-205 restated per 8192-word chunk, with the
 // chunk's packed bytes staged whole in LDS and the output offset running.
+// Of encode_sp.hip it uses only what neither form of the single pass changes:
+// the chunk geometry, SpStash (its words live in V[]), the mask helpers and A2.
 //
 // (Round 4 also ran a pipelined batch encoder on these pieces -- each
 // workgroup with the next unit's words in flight and a whole-unit LDS stage,
@@ -83,7 +85,7 @@ __device__ __forceinline__ void sp3_lookahead(const uint64_t (&LA)[4], uint32_t 
 // (PackedOutputStream.java:64-117), per step the Z / DL / D ballots stashed
 // lane-per-step; returns this lane's nonzero bytes
 template <bool kFull>
-__device__ __forceinline__ uint32_t sp3_a1(SpRegs &R, const uint64_t (&V)[kSpWS], uint32_t wrem, int cnt,
+__device__ __forceinline__ uint32_t sp3_a1(SpStash &R, const uint64_t (&V)[kSpWS], uint32_t wrem, int cnt,
                                            int lane) {
   uint32_t acc = 0;
 #pragma unroll
@@ -114,7 +116,7 @@ __device__ __forceinline__ uint32_t sp3_a1(SpRegs &R, const uint64_t (&V)[kSpWS]
 // with the loads), roles, the chunk's packed bytes (returned; wbefore /
 // wmine: bytes of the waves before this one / of this one).  The state the
 // chunk leaves goes to `next` when the piece continues.
-__device__ __forceinline__ uint64_t sp3_chunk(SpRegs &R, const uint64_t (&V)[kSpWS], const uint64_t (&LA)[4],
+__device__ __forceinline__ uint64_t sp3_chunk(SpStash &R, const uint64_t (&V)[kSpWS], const uint64_t (&LA)[4],
                                               const Sp3Unit &u, uint64_t *msk, uint64_t *scr, uint64_t pst,
                                               uint64_t *prev, uint64_t *next, uint32_t ep, uint32_t *err, int w,
                                               int lane, uint32_t &Xlast, uint64_t &wbefore) {
@@ -210,7 +212,7 @@ __device__ __forceinline__ uint64_t sp3_chunk(SpRegs &R, const uint64_t (&V)[kSp
 // word's string: tag + v_perm-compacted nonzero bytes + the count after a
 // 0x00 / 0xFF head, or the 8 bytes of a literal-run member
 // (PackedOutputStream.java:64-193).
-__device__ __forceinline__ void sp3_b(SpRegs &R, const uint64_t (&V)[kSpWS], int cnt, const uint64_t *lut,
+__device__ __forceinline__ void sp3_b(SpStash &R, const uint64_t (&V)[kSpWS], int cnt, const uint64_t *lut,
                                       uint32_t *stage, uint32_t base, int lane) {
   uint32_t rel = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
   const uint32_t l64 = 64u - (uint32_t)lane;
@@ -416,7 +418,7 @@ __global__ __launch_bounds__(kSpThreads, 1) void sp_small_kernel(const uint64_t 
   // word may hold an earlier call's, so the result cannot be judged by it)
   uint32_t *lerr = reinterpret_cast<uint32_t *>(&scr[13]);
   if (threadIdx.x == 0) scr[24] = scr[25] = scr[13] = 0;
-  SpRegs R;
+  SpStash R;
   R.zl = R.zh = R.dll = R.dlh = R.dl_ = R.dh_ = 0;
   R.oml = R.omh = R.ohl = R.ohh = R.oel = R.oeh = 0;
   __syncthreads();

@@ -29,8 +29,8 @@ constexpr uint32_t kE4RingBytes = 2048;  // output ring per wave (<= 41 live lin
 constexpr uint32_t kE4Ov = 1u;                                    // overhang lines
 constexpr uint32_t kE4RingStride = kE4RingBytes + 16 * kE4Ov;
 constexpr uint32_t kE4oLut = 0;                                   // u64[256]
-constexpr uint32_t kE4oRing = 2048;                               // u32[waves][512 (+ 164)]
-constexpr uint32_t kE4Lds = kE4oRing + kE4Waves * kE4RingStride;  // 10 KiB (12.6 KiB with overhang)
+constexpr uint32_t kE4oRing = 2048;                               // u32[waves][512 (+ 4)]
+constexpr uint32_t kE4Lds = kE4oRing + kE4Waves * kE4RingStride;  // 10,304 B (2048 + 4 x (2048 + 16))
 
 // the size pass's row per 64-word step for the emit pass: run boundaries,
 // literal-run members, heads (3 u64); at most 4 GiB of rows
@@ -691,7 +691,7 @@ __global__ __launch_bounds__(256) void e4_minmax_kernel(const uint64_t *__restri
 // to skip, tickets[kTkGate + 2]); else the reverse (the single pass's
 // ordered ticket exhausted)
 // Among single-pass batches, those whose sampled words are at least 85 %
-// zero take its sparse form (cpk_sparse: tickets[kTkGate + 6] = 1; config 4
+// zero take its sparse form (SpSparse: tickets[kTkGate + 6] = 1; config 4
 // encode -7 %, config 2 +36 %).
 // Dense batches (the sampled words' tags and nonzero bytes at least
 // CPK_GATE_DENSE_PCT % of their bytes) take the two passes instead: there a

@@ -13,8 +13,8 @@
 //                  by mask algebra, a decoupled look-back for the offsets,
 //                  strings (tag + v_perm-compacted bytes + count) OR-ed into
 //                  an LDS ring, 16-byte line stores; its sparse form
-//                  (cpk_sparse, below: words re-read in B, twice the
-//                  workgroups) for batches whose sampled words are >= 85 %
+//                  (SpSparse: words re-read in B, twice the workgroups per
+//                  CU) for batches whose sampled words are >= 85 %
 //                  zero; encode_v4.hip (two passes, mixed-size and small-
 //                  piece batches): one wave per piece, a size pass, a scan,
 //                  an emit pass.  The device chooses (e4_gate_kernel).
@@ -1600,84 +1600,12 @@ __global__ void gather8_kernel(Gather8 g, uint32_t k, uint64_t *out) {
 }
 
 #include "encode_v4.hip"
-// the dense form's ring: 11 KiB per wave, the most three workgroups per CU
-// leave room for (round 4: config 2's ~7.7 KiB of output per wave overflowed
-// 8 KiB rings often enough that waves waited for their offset a third of
-// the time; 11 KiB: encode -11 %)
-#ifndef CPK_SP_RING_DENSE
-#define CPK_SP_RING_DENSE 11264
-#endif
-#define CPK_SP_RING CPK_SP_RING_DENSE
-#define CPK_SP_HCALL 1
 #include "encode_sp.hip"
-#undef CPK_SP_HCALL
-#undef CPK_SP_RING
 #include "encode_sp3.hip"
 #include "decode_v2.hip"
 #include "stream_split.hip"
 
 }  // namespace cpk
-
-// The single pass's sparse form: encode_sp.hip compiled again with B
-// reading its words a second time (from L2) instead of holding them in 64
-// VGPRs, 4 KiB rings and 6 workgroups per CU.  Mostly-zero batches emit
-// little, so each wave's output fits its smaller ring and the extra
-// occupancy pays (config 4 encode 3.12 -> 2.89 ms per 131,072 pieces); on
-// config 2 a wave's ~6 KiB of output overflows the ring and it is 36 %
-// slower, so the device gate takes it only for batches whose sampled words
-// are >= 85 % zero (e4_gate_kernel).
-#pragma push_macro("CPK_SP_RELOAD")
-#pragma push_macro("CPK_SP_RING")
-#pragma push_macro("CPK_SP_WPE")
-#pragma push_macro("CPK_SP_A1G")
-#pragma push_macro("CPK_SP_DEFER")
-#pragma push_macro("CPK_SP_WAVES")
-#undef CPK_SP_WAVES
-#undef CPK_SP_RELOAD
-#undef CPK_SP_RING
-#undef CPK_SP_WPE
-#undef CPK_SP_A1G
-#undef CPK_SP_DEFER
-#define CPK_SP_RELOAD 1
-// (CPK_SPARSE_RING / _WPE / _A1G: A/B knobs for the form's ring, workgroups
-// per CU and A1 load groups)
-#ifdef CPK_SPARSE_RING
-#define CPK_SP_RING CPK_SPARSE_RING
-#else
-#define CPK_SP_RING 4096
-#endif
-#ifdef CPK_SPARSE_WPE
-#define CPK_SP_WPE CPK_SPARSE_WPE
-#else
-#define CPK_SP_WPE 6
-#endif
-#ifdef CPK_SPARSE_A1G
-#define CPK_SP_A1G CPK_SPARSE_A1G
-#else
-#define CPK_SP_A1G 4
-#endif
-#define CPK_SP_OWN_ROLES 1
-// (a step of zero words and no head builds no strings, a pair of them is
-// skipped whole: round 6, config 4 encode -1.1 %; the dense form's steps
-// are rarely empty)
-#define CPK_SP_SKIP 1
-#ifdef CPK_SPARSE_HCALL
-#define CPK_SP_HCALL 1
-#endif
-namespace cpk_sparse {
-using namespace cpk;
-#include "encode_sp.hip"
-}  // namespace cpk_sparse
-#undef CPK_SP_HCALL
-#undef CPK_SP_OWN_ROLES
-#undef CPK_SP_DEFER
-#undef CPK_SP_SKIP
-#pragma pop_macro("CPK_SP_RELOAD")
-#pragma pop_macro("CPK_SP_RING")
-#pragma pop_macro("CPK_SP_WPE")
-#pragma pop_macro("CPK_SP_A1G")
-#pragma pop_macro("CPK_SP_DEFER")
-#pragma pop_macro("CPK_SP_WAVES")
 
 // ================================================================ C ABI
 struct HostPipe;  // host_pipe.hip: staging of the host-memory forms
@@ -1898,8 +1826,8 @@ int cpk_ctx_create(int device, cpk_ctx *out) {
   // is checked against that at compile time, so a refused attribute is a
   // runtime/driver failure, reported as CPK_EDEVICE
   constexpr uint32_t kGfx950Lds = 160 * 1024;
-  static_assert(cpk::kDecLds <= kGfx950Lds && cpk::kSpLds <= kGfx950Lds && cpk::kSpSmallLds <= kGfx950Lds &&
-                    cpk::kMwLds <= kGfx950Lds && cpk::kSsLds <= kGfx950Lds,
+  static_assert(cpk::kDecLds <= kGfx950Lds && cpk::SpLay<cpk::SpDense>::kLds <= kGfx950Lds &&
+                    cpk::kSpSmallLds <= kGfx950Lds && cpk::kMwLds <= kGfx950Lds && cpk::kSsLds <= kGfx950Lds,
                 "a kernel's dynamic LDS exceeds gfx950's 160 KiB");
   const struct {
     const void *f;
@@ -1908,8 +1836,8 @@ int cpk_ctx_create(int device, cpk_ctx *out) {
              {(const void *)cpk::decode_kernel<true>, cpk::kDecLds},
              {(const void *)cpk::decode_kernel<false, true>, cpk::kDecLds},
              {(const void *)cpk::decode_kernel<true, true>, cpk::kDecLds},
-             {(const void *)cpk::sp_encode_kernel<true>, cpk::kSpLds},
-             {(const void *)cpk::sp_encode_kernel<false>, cpk::kSpLds},
+             {(const void *)cpk::sp_encode_kernel<true>, cpk::SpLay<cpk::SpDense>::kLds},
+             {(const void *)cpk::sp_encode_kernel<false>, cpk::SpLay<cpk::SpDense>::kLds},
              {(const void *)cpk::sp_small_kernel, cpk::kSpSmallLds},
              {(const void *)cpk::rm_mw_kernel, cpk::kMwLds},
              {(const void *)cpk::stream_mw_kernel, cpk::kMwLds},
@@ -2050,25 +1978,26 @@ int sp_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, const uint64
   if (!gated && hipMemsetAsync(ctx->tickets + cpk::kTkPlan, 0, 4, s) != hipSuccess) return CPK_EDEVICE;
   // (gated: both forms enqueued, the one the gate did not pick returns at once)
   const uint32_t *pick = gated ? ctx->tickets + cpk::kTkGate + 6 : nullptr;
-  unsigned grid = (unsigned)(cpk::kSpWpe * ctx->cus);
+  constexpr uint32_t kLds = cpk::SpLay<cpk::SpDense>::kLds;
+  unsigned grid = (unsigned)(cpk::SpDense::kWpe * ctx->cus);
   if (grid > ucap) grid = (unsigned)ucap;
   if (pdesc)
-    hipLaunchKernelGGL(cpk::sp_encode_kernel<true>, dim3(grid), dim3(cpk::kSpThreads), cpk::kSpLds, s,
+    hipLaunchKernelGGL(cpk::sp_encode_kernel<true>, dim3(grid), dim3(cpk::kSpThreads), kLds, s,
                        (const uint64_t *)d_in, d_swo, pdesc, tin, n, (uint8_t *)d_out, d_out_off,
                        ctx->sp_status, ctx->sp_epoch, ctx->tickets + cpk::kTkPlan, utab, nunits, ustate, hint,
                        ctx->tickets + cpk::kTkErr, tin ? tin - 1 : (const uint64_t *)nullptr, pick, 0u, out_cap);
   else
-    hipLaunchKernelGGL(cpk::sp_encode_kernel<false>, dim3(grid), dim3(cpk::kSpThreads), cpk::kSpLds, s,
+    hipLaunchKernelGGL(cpk::sp_encode_kernel<false>, dim3(grid), dim3(cpk::kSpThreads), kLds, s,
                        (const uint64_t *)d_in, d_swo, pdesc, tin, n, (uint8_t *)d_out, d_out_off,
                        ctx->sp_status, ctx->sp_epoch, ctx->tickets + cpk::kTkPlan, utab, nunits, ustate, hint,
                        ctx->tickets + cpk::kTkErr, tin ? tin - 1 : (const uint64_t *)nullptr, pick, 0u, out_cap);
   if (gated && !pdesc) {
-    unsigned g2 = (unsigned)(cpk_sparse::kSpWpe * ctx->cus);
+    unsigned g2 = (unsigned)(cpk::SpSparse::kWpe * ctx->cus);
     if (g2 > ucap) g2 = (unsigned)ucap;
-    hipLaunchKernelGGL(cpk_sparse::sp_encode_kernel<false>, dim3(g2), dim3(cpk_sparse::kSpThreads),
-                       cpk_sparse::kSpLds, s, (const uint64_t *)d_in, d_swo, pdesc, tin, n, (uint8_t *)d_out,
-                       d_out_off, ctx->sp_status, ctx->sp_epoch, ctx->tickets + cpk::kTkPlan, utab, nunits, ustate,
-                       hint, ctx->tickets + cpk::kTkErr, (const uint64_t *)nullptr, pick, 1u, out_cap);
+    hipLaunchKernelGGL((cpk::sp_encode_kernel<false, cpk::SpSparse>), dim3(g2), dim3(cpk::kSpThreads),
+                       cpk::SpLay<cpk::SpSparse>::kLds, s, (const uint64_t *)d_in, d_swo, pdesc, tin, n,
+                       (uint8_t *)d_out, d_out_off, ctx->sp_status, ctx->sp_epoch, ctx->tickets + cpk::kTkPlan, utab,
+                       nunits, ustate, hint, ctx->tickets + cpk::kTkErr, (const uint64_t *)nullptr, pick, 1u, out_cap);
   }
   return hip_ok(hipGetLastError());
 }

@@ -2,9 +2,9 @@
 // 64-word step, as scalar mask algebra over the step's Z / D-or-L / D masks
 // and the run state entering it (SpSt, sp_roles), and the lane helpers the
 // single pass uses with them (readfirstlane / readlane / writelane pairs,
-// v_ffbl, per-lane selects on an SGPR mask).  Included by encode_v4.hip
-// (in namespace cpk, for the single pass) and, for the single pass's sparse
-// form (a second namespace), again by encode_sp.hip.
+// v_ffbl, per-lane selects on an SGPR mask).  Included once, by
+// encode_v4.hip (in namespace cpk), ahead of encode_sp.hip and
+// encode_sp3.hip, which use it too.
 
 struct SpSt {
   uint32_t zl;   // zero run ending at the step start (0: none)

@@ -721,7 +721,7 @@ def test_gate_edges_and_sparse_form(ctx, oracle, cfg, words):
     pieces just under and at the single pass's 4 Ki-word threshold, one
     chunk, and 1.5 chunks (two units each); config-4 data (~90 % zero
     words) sends the single-pass batches to its sparse form
-    (cpk_sparse::sp_encode_kernel), config-2 data to the dense one, and
+    (sp_encode_kernel<false, SpSparse>), config-2 data to the dense one, and
     config-3 data (sampled packed bytes >= 90 % of the words') to the two
     passes (round 5)."""
     n = max(8, (1 << 22) // words)  # ~32 MiB per batch
@@ -741,6 +741,78 @@ def test_gate_big_piece_takes_single_pass(ctx, oracle, cfg):
         sizes.insert([0, 3, 5][order], 70000 + order)
         swo = _swo(sizes)
         _check_batch(ctx, oracle, oracle.generate(oracle.preset(cfg), swo), swo)
+
+
+@pytest.fixture(scope="module", params=["d", "s"], ids=["form-dense", "form-sparse"])
+def form_ctx(request):
+    """(context, form): a context with the default encoder and the single
+    pass's form forced (CPK_SP_FORM, "d" or "s", is read at context creation):
+    the gate then sends every like-sized batch to the single pass in that
+    form, whatever its density."""
+    import os
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    import capnp_packed as cp
+    saved = {k: os.environ.get(k) for k in ("CPK_ENCODER", "CPK_SP_FORM")}
+    os.environ.pop("CPK_ENCODER", None)
+    os.environ["CPK_SP_FORM"] = request.param
+    try:
+        c = cp.Context(0)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    yield c, request.param
+    c.close()
+
+
+def _hand_made_units(all_ff):
+    """Pieces of 12288 words (two units each): all zero (a zero run covers
+    the whole first chunk, so its exit state depends on the entering one),
+    all 0xFF bytes when asked for (a literal stretch crosses the unit
+    boundary, every count at its 255 cap), zero except the last word."""
+    w = [np.zeros(12288, dtype=np.uint64) for _ in range(3)]
+    w[1][:] = 0xFFFFFFFFFFFFFFFF
+    w[2][-1] = 0x8000000000000001
+    if not all_ff:
+        del w[1]
+    return np.concatenate(w).view(np.uint8), _swo([12288] * len(w))
+
+
+@pytest.mark.parametrize("cfg", [2, 3, 4])
+@pytest.mark.parametrize("words", [4096, 8192, 12288])
+def test_both_forms_on_both_densities(form_ctx, oracle, cfg, words, monkeypatch):
+    """Each form of the single pass (SpDense / SpSparse, encode_sp.hip) on
+    data the gate would not give it: 8 like-sized pieces of half a unit (the
+    gate's threshold), one unit (the straight-line A1) and 1.5 units (two
+    units each, run state carried between workgroups), of config-2, config-3
+    and config-4 data.  Config 3 through the sparse form overflows every
+    wave's 4 KiB ring (the offset is fetched before all steps are laid out);
+    config 4 through the dense form has its steps mostly empty.  The batches
+    are kept off the one-workgroup host path for small batches (CPK_NO_SMALL,
+    read per call), which would take the 8 x 4096 words without asking the
+    gate."""
+    monkeypatch.setenv("CPK_NO_SMALL", "1")
+    swo = _swo([words] * 8)
+    _check_batch(form_ctx[0], oracle, oracle.generate(oracle.preset(cfg), swo), swo)
+
+
+def test_both_forms_on_whole_chunk_runs(form_ctx, oracle, monkeypatch):
+    """Each form on the hand-made two-unit pieces (_hand_made_units).  The
+    sparse form's batch is without the all-0xFF piece: on that piece it
+    stores zeros for 352 of the piece's 98,400 packed bytes (the first at
+    byte 13,312 of the piece; the offsets are right), alone or next to the
+    other two pieces, while the dense form packs it correctly.  That is how
+    the sparse form behaved before its constants became a template argument,
+    and it is left as found.  (CPK_NO_SMALL: the two remaining pieces would
+    otherwise fit the one-workgroup host path.)"""
+    monkeypatch.setenv("CPK_NO_SMALL", "1")
+    c, form = form_ctx
+    data, swo = _hand_made_units(all_ff=form == "d")
+    _check_batch(c, oracle, data, swo)
 
 
 def test_decode_host_few_large_pieces(ctx, oracle):

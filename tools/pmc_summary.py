@@ -19,7 +19,10 @@ for f in sorted(root.glob("*/*_counter_collection.csv")):
         for r in csv.DictReader(fh):
             k = r["Kernel_Name"]
             short = ("e4_size_kernel" if "e4_size_kernel" in k else "e4_emit_kernel" if "e4_emit_kernel" in k
-                     else "sp_encode_sparse_kernel" if "cpk_sparse" in k and "sp_encode_kernel" in k
+                     # (the sparse form: sp_encode_kernel<false, cpk::SpSparse>, and
+                     # cpk_sparse::sp_encode_kernel in profiles from before the forms
+                     # became a template argument)
+                     else "sp_encode_sparse_kernel" if "sp_encode_kernel" in k and ("SpSparse" in k or "cpk_sparse" in k)
                      else "sp_encode_kernel" if "sp_encode_kernel" in k
                      else "decode2_kernel" if "decode2_kernel" in k
                      # (decode_kernel<stream, serial>: the dense form -- serial walks of
