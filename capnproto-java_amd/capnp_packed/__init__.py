@@ -38,8 +38,10 @@ EXPORTS = [
     "cpk_decode_messages_host", "cpk_encode_host_gather", "cpk_encode_messages_host_gather",
     "cpk_read_message", "cpk_read_message_host", "cpk_ctx_small_fallbacks",
     "cpk_encode_batch_cap", "cpk_encode_messages_cap", "cpk_ctx_dense_windows",
+    "cpk_decode_message_stream", "cpk_decode_message_stream_host",
 ]
 MSG_HEAD_WORDS, MSG_INFO_WORDS = 257, 517  # CPK_MSG_HEAD_WORDS, CPK_MSG_INFO_WORDS
+MS_INFO_WORDS = 5  # CPK_MS_INFO_WORDS
 
 
 class CodecError(RuntimeError):
@@ -107,6 +109,8 @@ def load(path: Path | None = None, strict: bool = True) -> ctypes.CDLL:
         "cpk_decode_messages_host": ([vp, vp, vp, u32, u64, vp, u64, vp, u32, vp, vp, vp], i32),
         "cpk_read_message": ([vp, vp, u64, u64, vp, u64, vp, vp], i32),
         "cpk_read_message_host": ([vp, vp, u64, u64, vp, u64, vp], i32),
+        "cpk_decode_message_stream": ([vp, vp, u64, u64, vp, u64, vp, vp, u32, vp, vp, u32, vp, vp], i32),
+        "cpk_decode_message_stream_host": ([vp, vp, u64, u64, vp, u64, vp, vp, u32, vp, vp, u32, vp], i32),
     }
     for name, (args, res) in sig.items():
         if not strict and not hasattr(L, name):
@@ -479,6 +483,65 @@ def _read_message_host(self, packed, out_cap_words: int | None = None,
 
 Context.read_message = _read_message
 Context.read_message_host = _read_message_host
+
+
+def _decode_message_stream(self, d_packed, avail: int, d_out, d_msg_off, d_msg_seg_off, d_seg_begin,
+                           d_seg_words, traversal_limit_words: int = 8 * 1024 * 1024, stream=None):
+    """cpk_decode_message_stream: a loop of SerializePacked.read over a
+    device-resident stream of packed messages whose boundaries are not known.
+    d_out gets the flat unpacked stream; segment j is d_out[d_seg_begin[j] :
+    + d_seg_words[j]].  Capacities come from the tensors' sizes (None: 0).
+    -> (rc, info): rc CPK_OK or CPK_ENOMEM (info then holds the sizes
+    needed); info = [messages, segments, words, bytes consumed, tail status]."""
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+
+    def words(t):
+        return t.numel() * t.element_size() // 8 if t is not None else 0
+    msg_cap = max(min(words(d_msg_off), words(d_msg_seg_off)) - 1, 0)
+    seg_cap = min(words(d_seg_begin), words(d_seg_words))
+    if words(d_msg_off) == 0 or words(d_msg_seg_off) == 0:
+        d_msg_off = d_msg_seg_off = None
+    info = np.zeros(MS_INFO_WORDS, np.uint64)
+    rc = self._lib.cpk_decode_message_stream(
+        self.handle, d_packed.data_ptr(), int(avail), int(traversal_limit_words), ptr(d_out), words(d_out),
+        ptr(d_msg_off), ptr(d_msg_seg_off), msg_cap, ptr(d_seg_begin), ptr(d_seg_words), seg_cap,
+        info.ctypes.data, self._stream(stream))
+    if rc not in (OK, ENOMEM):
+        _check(rc, "cpk_decode_message_stream")
+    out = [int(v) for v in info]
+    out[4] = int(info.view(np.int64)[4])
+    return rc, out
+
+
+def _decode_message_stream_host(self, packed, traversal_limit_words: int = 8 * 1024 * 1024):
+    """cpk_decode_message_stream_host -> (tail status, [[segment bytes]],
+    bytes consumed): every complete message of the stream, in order.  Sized
+    by the CPK_ENOMEM protocol: the words first, then the arrays."""
+    pk = np.ascontiguousarray(np.frombuffer(bytes(packed), np.uint8) if not isinstance(packed, np.ndarray)
+                              else packed, dtype=np.uint8)
+    info = np.zeros(MS_INFO_WORDS, np.uint64)
+    words = nm = ns = 0
+    for _ in range(3):
+        out = np.zeros(max(words, 1), np.uint64)
+        mo, mso = np.zeros(nm + 1, np.uint64), np.zeros(nm + 1, np.uint64)
+        sb, sw = np.zeros(max(ns, 1), np.uint64), np.zeros(max(ns, 1), np.uint64)
+        rc = self._lib.cpk_decode_message_stream_host(
+            self.handle, pk.ctypes.data if pk.size else None, pk.size, int(traversal_limit_words),
+            out.ctypes.data, words, mo.ctypes.data, mso.ctypes.data, nm, sb.ctypes.data, sw.ctypes.data, ns,
+            info.ctypes.data)
+        if rc != ENOMEM:
+            break
+        words, nm, ns = max(words, int(info[2])), max(nm, int(info[0])), max(ns, int(info[1]))
+    _check(rc, "cpk_decode_message_stream_host")
+    b = out.view(np.uint8)
+    msgs = [[b[8 * int(sb[j]): 8 * int(sb[j] + sw[j])].tobytes() for j in range(int(mso[m]), int(mso[m + 1]))]
+            for m in range(int(info[0]))]
+    return int(info.view(np.int64)[4]), msgs, int(info[3])
+
+
+Context.decode_message_stream = _decode_message_stream
+Context.decode_message_stream_host = _decode_message_stream_host
 
 
 def gen_params(cfg: int, z: float, lz: float, q: float) -> GenParams:

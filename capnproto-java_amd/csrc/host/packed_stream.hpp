@@ -450,6 +450,55 @@ struct SerializePacked {
         res[m].emplace_back(out.begin() + 8 * swo[j], out.begin() + 8 * swo[j + 1]);
     return res;
   }
+
+  // A loop of read() over bytes that hold message after message with nothing
+  // between them -- a log file, a drained socket buffer -- in ONE GPU pass
+  // (cpk_decode_message_stream_host): the device finds the messages itself.
+  // Every complete message in front of the first that fails; `consumed` is
+  // where the last of them ends, `tail` CPK_OK when that is the end of the
+  // bytes, else what the next read() would throw (CPK_ETRUNC: the bytes end
+  // inside a message -- a channel reader keeps them and reads on).
+  struct ReadAllResult {
+    std::vector<Message> messages;
+    uint64_t consumed = 0;
+    int tail = CPK_OK;
+  };
+  static ReadAllResult readAll(Gpu &gpu, const uint8_t *bytes, size_t size,
+                               uint64_t traversal_limit_words = 8ull << 20) {
+    uint64_t info[CPK_MS_INFO_WORDS] = {0, 0, 0, 0, 0};
+    std::vector<uint64_t> words, mo(1), mso(1), sb, sw;
+    int rc = CPK_ENOMEM;
+    // sized by the call itself: the words first, then the arrays
+    for (int pass = 0; pass < 3 && rc == CPK_ENOMEM; ++pass) {
+      rc = cpk_decode_message_stream_host(gpu.get(), bytes, size, traversal_limit_words, words.data(), words.size(),
+                                          mo.data(), mso.data(), (uint32_t)mo.size() - 1, sb.data(), sw.data(),
+                                          (uint32_t)sb.size(), info);
+      if (rc != CPK_ENOMEM) break;
+      if (info[2] > words.size()) words.resize(info[2]);
+      if (info[0] + 1 > mo.size()) {
+        mo.resize(info[0] + 1);
+        mso.resize(info[0] + 1);
+      }
+      if (info[1] > sb.size()) {
+        sb.resize(info[1]);
+        sw.resize(info[1]);
+      }
+    }
+    check(rc, "SerializePacked.readAll");
+    ReadAllResult res;
+    res.consumed = info[3];
+    res.tail = (int)(int64_t)info[4];
+    res.messages.resize(info[0]);
+    const uint8_t *w = reinterpret_cast<const uint8_t *>(words.data());
+    for (uint64_t m = 0; m < info[0]; ++m)
+      for (uint64_t j = mso[m]; j < mso[m + 1]; ++j)
+        res.messages[m].emplace_back(w + 8 * sb[j], w + 8 * (sb[j] + sw[j]));
+    return res;
+  }
+  static ReadAllResult readAll(Gpu &gpu, const std::vector<uint8_t> &bytes,
+                               uint64_t traversal_limit_words = 8ull << 20) {
+    return readAll(gpu, bytes.data(), bytes.size(), traversal_limit_words);
+  }
 };
 
 }  // namespace capnp_amd

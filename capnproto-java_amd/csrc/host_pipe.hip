@@ -963,3 +963,63 @@ int cpk_decode_messages_host(cpk_ctx ctx, const void *h_packed, const uint64_t *
 }
 
 }  // extern "C"
+
+// A whole stream of packed messages from host memory
+// (cpk_decode_message_stream): the bytes staged through the pinned slot 0 as
+// cpk_decode_stream_host stages them, the device call, then the complete
+// messages' words and the four arrays copied back.
+extern "C" {
+
+int cpk_decode_message_stream_host(cpk_ctx ctx, const void *h_packed, uint64_t avail,
+                                   uint64_t traversal_limit_words, void *h_out, uint64_t out_cap_words,
+                                   uint64_t *h_msg_off, uint64_t *h_msg_seg_off, uint32_t msg_cap,
+                                   uint64_t *h_seg_begin, uint64_t *h_seg_words, uint32_t seg_cap,
+                                   uint64_t *h_info) {
+  if (!ctx || !h_info || (avail && !h_packed) || (out_cap_words && !h_out)) return CPK_EINVAL;
+  if ((seg_cap && (!h_seg_begin || !h_seg_words)) || (msg_cap && (!h_msg_off || !h_msg_seg_off))) return CPK_EINVAL;
+  for (int i = 0; i < CPK_MS_INFO_WORDS; ++i) h_info[i] = 0;
+  if (avail == 0) {
+    if (h_msg_off) h_msg_off[0] = 0;
+    if (h_msg_seg_off) h_msg_seg_off[0] = 0;
+    return CPK_OK;
+  }
+  DeviceGuard g(ctx->device);
+  const bool marr = h_msg_off && h_msg_seg_off, sarr = h_seg_begin && h_seg_words;
+  // meta: msg_off [msg_cap + 1] | msg_seg_off [msg_cap + 1] | seg_begin [seg_cap] | seg_words [seg_cap]
+  const uint64_t mc = marr ? msg_cap + 1ull : 0, sc = sarr ? seg_cap : 0;
+  HostPipe *p = nullptr;
+  int rc = pipe_get(ctx, avail, out_cap_words * 8, 2 * mc + 2 * sc + 1, &p, 1);
+  if (rc) return rc;
+  HostSlot &sl = p->slot[0];
+  uint64_t *m = sl.pin_meta, *dm = sl.d_meta;
+  memset((uint8_t *)sl.pin_in + avail, 0, 64);  // (the decoder's read slack)
+  if (h2d_pipelined(sl.d_in, sl.pin_in, h_packed, avail, p->sk) ||
+      hipMemcpyAsync((uint8_t *)sl.d_in + avail, (uint8_t *)sl.pin_in + avail, 64, hipMemcpyHostToDevice, p->sk))
+    return CPK_EDEVICE;
+  rc = cpk_decode_message_stream(ctx, sl.d_in, avail, traversal_limit_words, sl.d_out, out_cap_words,
+                                 marr ? dm : nullptr, marr ? dm + mc : nullptr, marr ? msg_cap : 0,
+                                 sarr ? dm + 2 * mc : nullptr, sarr ? dm + 2 * mc + sc : nullptr, sarr ? seg_cap : 0,
+                                 h_info, p->sk);
+  if (rc) {
+    pipe_drain(p);
+    return rc;
+  }
+  const uint64_t nm = h_info[0], ns = h_info[1], words = h_info[2];
+  if (hipMemcpyAsync(m, dm, (2 * mc + 2 * sc) * 8ull, hipMemcpyDeviceToHost, p->sk)) return CPK_EDEVICE;
+  if (words) {
+    if (d2h_pipelined(h_out, sl.pin_out, sl.d_out, words * 8, p->sk, sl.eh, sl.ed)) return CPK_EDEVICE;
+  } else if (hipStreamSynchronize(p->sk)) {
+    return CPK_EDEVICE;
+  }
+  if (marr) {
+    memcpy(h_msg_off, m, (nm + 1) * 8);
+    memcpy(h_msg_seg_off, m + mc, (nm + 1) * 8);
+  }
+  if (sarr) {
+    memcpy(h_seg_begin, m + 2 * mc, ns * 8);
+    memcpy(h_seg_words, m + 2 * mc + sc, ns * 8);
+  }
+  return CPK_OK;
+}
+
+}  // extern "C"

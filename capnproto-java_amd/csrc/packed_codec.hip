@@ -1629,6 +1629,8 @@ struct cpk_ctx_s {
   HostPipe *pipe;         // cpk_encode_host / cpk_decode_host staging (lazy)
   uint64_t *ss_buf;       // parallel stream decode scratch (stream_split.hip)
   uint64_t ss_cap;        //   u64 entries
+  uint64_t *ms_buf;       // cpk_decode_message_stream: the frame chain's entries and result row (lazy)
+  uint64_t ms_cap;        //   entries (messages)
   uint64_t *rm_buf;       // cpk_read_message: piece word offsets | piece ends | statuses (lazy)
   uint64_t *fl_buf;       // cpk_decode_batch of a few large pieces: boundaries found [33] (lazy)
   uint64_t *probe_pin;    // host read-backs of a few device words (read_words): pinned [8] (lazy)
@@ -1869,6 +1871,7 @@ void cpk_ctx_destroy(cpk_ctx ctx) {
   if (ctx->sp_status) hipFree(ctx->sp_status);
   if (ctx->sp_desc) hipFree(ctx->sp_desc);
   if (ctx->ss_buf) hipFree(ctx->ss_buf);
+  if (ctx->ms_buf) hipFree(ctx->ms_buf);
   if (ctx->rm_buf) hipFree(ctx->rm_buf);
   if (ctx->fl_buf) hipFree(ctx->fl_buf);
   if (ctx->probe_pin) hipHostFree(ctx->probe_pin);
@@ -2375,13 +2378,10 @@ uint64_t ss_reach(uint64_t avail, uint64_t words) {
   return avail < b ? avail : b;
 }
 
-// parallel stream decode over at most `reach` bytes; enqueues the one-wave
-// decoder after it, which runs only if the parallel path met anything
-// irregular (it then decodes the whole stream, errors included)
-int ss_decode(cpk_ctx ctx, const uint8_t *pk, uint64_t avail, uint64_t reach, const uint64_t *swo, uint32_t n,
-              uint64_t *out, uint64_t *in_off, int32_t *status, hipStream_t s) {
+// the block map's scratch for nb blocks, in the context (grown on demand)
+int ss_bufs(cpk_ctx ctx, uint64_t nb, cpk::SsBufs &B) {
   using namespace cpk;
-  const uint64_t nb = (reach + kSsBlock - 1) / kSsBlock, ng = (nb + kSsGroup - 1) / kSsGroup;
+  const uint64_t ng = (nb + kSsGroup - 1) / kSsGroup;
   // scratch layout (u64 entries)
   const uint64_t need = 5 * nb + 3 * kSsCand * nb + (nb + 1) / 2 + 3 * kSsVar * ng + (kSsVar + 1) * nb +
                         ((kSsVar + 1) * nb + 1) / 2 + (ng + 1) / 2 + ng + 4 * (nb + 1) + (nb + 1) / 2 + 2 + 2;
@@ -2399,7 +2399,6 @@ int ss_decode(cpk_ctx ctx, const uint8_t *pk, uint64_t avail, uint64_t reach, co
     q += k;
     return r;
   };
-  SsBufs B;
   B.X = take(nb);
   B.W = take(nb);
   B.C1 = take(nb);
@@ -2423,6 +2422,18 @@ int ss_decode(cpk_ctx ctx, const uint8_t *pk, uint64_t avail, uint64_t reach, co
   B.sst = (int32_t *)take((nb + 1) / 2);
   B.flag = (uint32_t *)take(2);
   B.lim = take(2);
+  return CPK_OK;
+}
+
+// parallel stream decode over at most `reach` bytes; enqueues the one-wave
+// decoder after it, which runs only if the parallel path met anything
+// irregular (it then decodes the whole stream, errors included)
+int ss_decode(cpk_ctx ctx, const uint8_t *pk, uint64_t avail, uint64_t reach, const uint64_t *swo, uint32_t n,
+              uint64_t *out, uint64_t *in_off, int32_t *status, hipStream_t s) {
+  using namespace cpk;
+  const uint64_t nb = (reach + kSsBlock - 1) / kSsBlock, ng = (nb + kSsGroup - 1) / kSsGroup;
+  SsBufs B;
+  if (int rc = ss_bufs(ctx, nb, B)) return rc;
   if (hipMemsetAsync(B.N2, 0, 4 * nb, s) != hipSuccess || hipMemsetAsync(B.flag, 0, 8, s) != hipSuccess ||
       hipMemsetAsync(ctx->tickets + kTkDec, 0, 8 * kTkStride * 4, s) != hipSuccess)
     return CPK_EDEVICE;
@@ -2480,6 +2491,110 @@ int cpk_decode_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
   return hip_ok(hipGetLastError());
 }
 
+
+// A whole stream of packed messages (stream_split.hip, ms_*): the block map
+// over every byte, the blocks decoded into d_out, the frame chain, every
+// piece boundary checked, the result row read back (the one sync; a second
+// only when the chain made more entries than the context had room for).
+int cpk_decode_message_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail, uint64_t traversal_limit_words,
+                              void *d_out, uint64_t out_cap_words, uint64_t *d_msg_off, uint64_t *d_msg_seg_off,
+                              uint32_t msg_cap, uint64_t *d_seg_begin, uint64_t *d_seg_words, uint32_t seg_cap,
+                              uint64_t *h_info, void *stream) {
+  using namespace cpk;
+  if (!ctx || !h_info || (avail && !d_packed) || (out_cap_words && !d_out)) return CPK_EINVAL;
+  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_msg_off & 7) ||
+      ((uintptr_t)d_msg_seg_off & 7) || ((uintptr_t)d_seg_begin & 7) || ((uintptr_t)d_seg_words & 7))
+    return CPK_EINVAL;
+  if (seg_cap && (!d_seg_begin || !d_seg_words)) return CPK_EINVAL;
+  if (msg_cap && (!d_msg_off || !d_msg_seg_off)) return CPK_EINVAL;
+  for (int i = 0; i < CPK_MS_INFO_WORDS; ++i) h_info[i] = 0;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (avail == 0) {
+    if ((d_msg_off && hipMemsetAsync(d_msg_off, 0, 8, s) != hipSuccess) ||
+        (d_msg_seg_off && hipMemsetAsync(d_msg_seg_off, 0, 8, s) != hipSuccess))
+      return CPK_EDEVICE;
+    return CPK_OK;
+  }
+  // (entries the arrays hold: msg_cap + 1 and seg_cap; none without an array)
+  const int64_t msg_lim = d_msg_off && d_msg_seg_off ? (int64_t)msg_cap : -1;
+  const int64_t seg_lim = d_seg_begin && d_seg_words ? (int64_t)seg_cap : 0;
+  const uint64_t nb = (avail + kSsBlock - 1) / kSsBlock, ng = (nb + kSsGroup - 1) / kSsGroup;
+  SsBufs B;
+  if (int rc = ss_bufs(ctx, nb, B)) return rc;
+  // the chain's entries: a message per 64 packed bytes to begin with
+  auto ms_bufs = [&](uint64_t entries, MsBufs &M) {
+    if (entries > ctx->ms_cap) {
+      if (ctx->ms_buf) hipFree(ctx->ms_buf);
+      ctx->ms_buf = nullptr;
+      ctx->ms_cap = 0;
+      const uint64_t cap = entries + entries / 4;
+      if (hipMalloc(&ctx->ms_buf, (16 + 3 * cap + (cap + 1) / 2) * 8) != hipSuccess) return CPK_ENOMEM;
+      ctx->ms_cap = cap;
+    }
+    M.mcap = ctx->ms_cap;
+    M.ctl = ctx->ms_buf;
+    M.res = M.ctl + 8;
+    M.X = M.res + 8;
+    M.S = M.X + M.mcap;
+    M.P = M.S + M.mcap;
+    M.ST = (int32_t *)(M.P + M.mcap);
+    return CPK_OK;
+  };
+  MsBufs M;
+  if (int rc = ms_bufs(avail / 64 + 1024, M)) return rc;
+  if (hipMemsetAsync(B.N2, 0, 4 * nb, s) != hipSuccess || hipMemsetAsync(B.flag, 0, 8, s) != hipSuccess ||
+      hipMemsetAsync(ctx->tickets + kTkDec, 0, 8 * kTkStride * 4, s) != hipSuccess)
+    return CPK_EDEVICE;
+  const uint8_t *pk = (const uint8_t *)d_packed;
+  const uint64_t *out = (const uint64_t *)d_out;
+  const unsigned tb = 256, gb = (unsigned)((nb + tb - 1) / tb);
+  const uint64_t nsub = (nb + kSsSub - 1) / kSsSub;
+  hipLaunchKernelGGL(ss_scan_kernel, dim3((unsigned)ng), dim3(kSsThreads), kSsLds, s, pk, avail,
+                     (const uint64_t *)nullptr, 0u, nb, B);
+  hipLaunchKernelGGL(ss_group_kernel, dim3((unsigned)ng), dim3(64), 0, s, pk, nb, B);
+  hipLaunchKernelGGL(ss_top_kernel, dim3(1), dim3(64), 0, s, pk, nb, B);
+  hipLaunchKernelGGL(ss_cut_kernel, dim3(gb), dim3(tb), 0, s, nb, B);
+  hipLaunchKernelGGL(ms_end_kernel, dim3(1), dim3(64), 0, s, pk, nb, out_cap_words, B, M);
+  hipLaunchKernelGGL(ms_sub_kernel, dim3((unsigned)((nsub + 1 + tb - 1) / tb)), dim3(tb), 0, s, nb, B, M);
+  dec_launch(ctx, false, (unsigned)((nsub + 3) / 4), pk, B.sin, B.sswo, (uint32_t)nsub, (uint64_t *)d_out, B.sst, 0,
+             DecStreams{nullptr, nullptr, nullptr, 0, nullptr}, s);
+  hipLaunchKernelGGL(ss_check_kernel, dim3((unsigned)((nsub + tb - 1) / tb)), dim3(tb), 0, s, nsub, B);
+  uint64_t r[8];
+  for (int attempt = 0;; ++attempt) {
+    const unsigned waves = (unsigned)((M.mcap + 3) / 4), bgrid = waves < 8u * ctx->cus ? waves : 8u * ctx->cus;
+    hipLaunchKernelGGL(ms_chain_kernel, dim3(1), dim3(64), 0, s, out, nb, B, M, traversal_limit_words,
+                       d_msg_seg_off, msg_lim, d_seg_begin, d_seg_words, seg_lim);
+    hipLaunchKernelGGL(ms_bound_kernel, dim3(bgrid), dim3(256), 0, s, pk, out, nb, B, M, traversal_limit_words,
+                       d_msg_off, msg_lim);
+    hipLaunchKernelGGL(ms_final_kernel, dim3(1), dim3(64), 0, s, nb, B, M);
+    if (hipGetLastError() != hipSuccess) return CPK_EDEVICE;
+    if (int rc = read_words(ctx, s, {M.res, M.res + 1, M.res + 2, M.res + 3, M.res + 4, M.res + 5, M.res + 6,
+                                    M.res + 7}, r))
+      return rc;
+    if (!(r[6] & kMsShort) || attempt) break;
+    // more messages than entries: the chain and the checks again with room
+    // for all (the map and the words stay as they are)
+    if (int rc = ms_bufs(r[5], M)) return rc;
+    hipLaunchKernelGGL(ms_rearm_kernel, dim3(1), dim3(64), 0, s, M);
+  }
+  h_info[2] = r[7];
+  if (r[6] & kMsNoRoom) return CPK_ENOMEM;
+  if (r[6] & kMsShort) return CPK_EDEVICE;
+  if (r[6]) {
+    // the batch decoder rejected a block of the map (no such stream is known)
+    h_info[2] = 0;
+    h_info[4] = (uint64_t)(int64_t)CPK_EUNSUPPORTED;
+    return CPK_EUNSUPPORTED;
+  }
+  h_info[0] = r[0];
+  h_info[1] = r[1];
+  if ((int64_t)r[0] > msg_lim || (int64_t)r[1] > seg_lim) return CPK_ENOMEM;
+  h_info[2] = r[2];
+  h_info[3] = r[3];
+  h_info[4] = r[4];
+  return CPK_OK;
+}
 }  // extern "C"
 static int read_message_impl(cpk_ctx ctx, const void *d_packed, uint64_t avail, uint64_t traversal_limit_words,
                              void *d_out, uint64_t out_cap_words, uint64_t *d_info, void *stream,

@@ -191,11 +191,12 @@ __global__ __launch_bounds__(kSsThreads) void ss_scan_kernel(const uint8_t *__re
                                                      const uint64_t *__restrict__ swo, uint32_t n, uint64_t nbmax,
                                                      SsBufs B) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const uint64_t R = ss_R(swo, n, avail);
+  // (swo null -- the message stream, ms_* below: every byte, all the words)
+  const uint64_t R = swo ? ss_R(swo, n, avail) : avail;
   const uint32_t t = threadIdx.x;
   if (blockIdx.x == 0 && t == 0) {
     B.lim[0] = R;
-    B.lim[1] = swo[n] - swo[0];
+    B.lim[1] = swo ? swo[n] - swo[0] : kSsInf;
   }
   const uint64_t nb = min(nbmax, (R + kSsBlock - 1) / kSsBlock);
   const uint64_t b0 = (uint64_t)blockIdx.x * kSsGroup;
@@ -582,4 +583,292 @@ __global__ __launch_bounds__(256) void ss_final_kernel(uint32_t n, int32_t *__re
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if ((!bad || no_fallback) && i < n) status[i] = bad ? CPK_EUNSUPPORTED : CPK_OK;
   if (blockIdx.x == 0 && threadIdx.x < 8) tickets[threadIdx.x * kTkStride] = (bad && !no_fallback) ? 0u : 0x40000000u;
+}
+
+// ---- a stream of packed messages (cpk_decode_message_stream) ---------------
+// A loop of SerializePacked.read over bytes whose message boundaries are not
+// known (SerializePacked.java:51-66, Serialize.java:119-178): each message's
+// piece sizes are inside the stream.  The block map above is made over every
+// byte (ss_scan with no piece sizes), the blocks are decoded as batch pieces
+// into the caller's buffer -- the flat unpacked stream: each message's table
+// words, then its segments -- and then
+//   ms_chain  one wave follows the messages through the unpacked words: the
+//             first table word gives the segment count, the sizes are read 64
+//             at a time and scanned into the segments' places.  It stops at
+//             the end of the words or at the first message whose table is
+//             invalid or which needs more words than there are (the last
+//             entry it makes: the stream's end, or the failing message);
+//   ms_bound  a wave per message: every piece boundary of the message (first
+//             table word, rest of the table, each segment) as a record start,
+//             found by a search of the blocks' first words and a walk of
+//             records, as ss_bound does it.  The walk keeps the reference's
+//             order of checks (oracle/packed_oracle.c:cpko_unpack), so the
+//             status of a message that fails is the one its read() throws;
+//   ms_final  the first failing message ends the stream: the result row.
+// A record cut by the end of the bytes is not in the map (the walks stop in
+// front of it): the blocks behind it are decoded up to it (ms_end finds the
+// place), and the message it belongs to fails in ms_bound's walk.
+struct MsBufs {
+  uint64_t *ctl;  // [0] entries the chain made, [1] first failing entry, [2] end of the whole records, [3] flags
+  uint64_t *res;  // the result row [8]
+  uint64_t *X;    // per entry: its first word in the flat stream [mcap]
+  uint64_t *S;    //   segments before it [mcap]
+  uint64_t *P;    //   its first packed byte [mcap]
+  int32_t *ST;    //   its status [mcap]
+  uint64_t mcap;
+};
+constexpr uint64_t kMsNoRoom = 1, kMsIrregular = 4, kMsShort = 8;  // flags: out_cap_words; the map; mcap
+
+__device__ __forceinline__ uint64_t ss_nb(const SsBufs &B, uint64_t nbmax) {
+  return min(nbmax, (B.lim[0] + kSsBlock - 1) / kSsBlock);
+}
+// the last block in [0, nb] that starts at a true record with at most T words before it
+__device__ __forceinline__ uint64_t ms_block(const SsBufs &B, uint64_t nb, uint64_t T) {
+  uint64_t lo = 0, hi = nb;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi + 1) / 2;
+    if (B.WO[mid] <= T && B.E[mid] != kSsInf) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// one thread: where the whole records end, the capacity check, the row cleared
+__global__ void ms_end_kernel(const uint8_t *__restrict__ pk, uint64_t nbmax, uint64_t out_cap_words, SsBufs B,
+                              MsBufs M) {
+  if (threadIdx.x || blockIdx.x) return;
+  const uint64_t R = B.lim[0], nb = ss_nb(B, nbmax), W = B.WO[nb];
+  const uint64_t lo = ms_block(B, nb, kSsInf);
+  uint64_t p = B.E[lo], w = B.WO[lo];
+  while (p < R && ss_step(SsGlobal{pk, R}, R, p, w)) {
+  }
+  M.ctl[0] = 0;
+  M.ctl[1] = kSsInf;
+  M.ctl[2] = p;
+  M.ctl[3] = (w != W || p > R ? kMsIrregular : 0) | (W > out_cap_words ? kMsNoRoom : 0);
+  for (int i = 0; i < 8; ++i) M.res[i] = 0;
+}
+
+// the blocks, kSsSub at a time, as batch pieces (none when the words do not fit)
+__global__ __launch_bounds__(256) void ms_sub_kernel(uint64_t nbmax, SsBufs B, MsBufs M) {
+  const uint64_t nb = ss_nb(B, nbmax);
+  const uint64_t nsub = (nbmax + kSsSub - 1) / kSsSub;
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > nsub) return;
+  const uint64_t b = min(k * kSsSub, nb);
+  uint64_t e = 0, wo = 0;
+  if (M.ctl[3] == 0) {
+    e = b < nb && B.E[b] != kSsInf ? B.E[b] : M.ctl[2];
+    wo = B.WO[b];
+  }
+  B.sin[k] = e;
+  B.sswo[k] = wo;
+}
+
+// the chain's control words for a second run with more entries (in a new
+// buffer; a run with a flag set does not get here)
+__global__ void ms_rearm_kernel(MsBufs M) {
+  if (threadIdx.x || blockIdx.x) return;
+  M.ctl[0] = 0;
+  M.ctl[1] = kSsInf;
+  M.ctl[2] = M.ctl[3] = 0;
+  for (int i = 0; i < 8; ++i) M.res[i] = 0;
+}
+
+// (msg_lim / seg_lim: entries the caller's arrays hold, -1 with no array)
+__global__ __launch_bounds__(64) void ms_chain_kernel(const uint64_t *__restrict__ out, uint64_t nbmax, SsBufs B,
+                                                      MsBufs M, uint64_t limit, uint64_t *__restrict__ msg_seg_off,
+                                                      int64_t msg_lim, uint64_t *__restrict__ seg_begin,
+                                                      uint64_t *__restrict__ seg_words, int64_t seg_lim) {
+  if (M.ctl[3] | B.flag[0]) return;
+  const int lane = (int)threadIdx.x;
+  const uint64_t W = B.WO[ss_nb(B, nbmax)];
+  uint64_t x = 0, m = 0, sb = 0;
+  // the message's first 64 words, a lane each: the first table word and, for
+  // up to 127 segments, the rest of the table in one round trip
+  uint64_t head = W ? out[min(x + (uint64_t)lane, W - 1)] : 0;
+  for (;;) {
+    if (lane == 0) {
+      if (m < M.mcap) {
+        M.X[m] = x;
+        M.S[m] = sb;
+      }
+      if ((int64_t)m <= msg_lim) msg_seg_off[m] = sb;
+    }
+    if (x >= W) break;
+    const uint64_t first = ss_rl64(head, 0);
+    const uint32_t raw = (uint32_t)first;
+    if (raw > 511u) break;
+    const uint32_t count = raw + 1, rest = (count & ~1u) / 2;
+    if (x + 1 + rest > W) break;
+    const uint64_t s0w = x + 1 + rest;
+    // segment i's size is u32 i + 1 of the table
+    auto round = [&](uint32_t base, uint64_t before, uint32_t &sz, uint64_t &beg) {
+      const uint32_t i = base + (uint32_t)lane, u = i + 1;
+      const uint64_t wv = base == 0 ? __shfl(head, (int)(u / 2) & 63, 64) : (i < count ? out[x + u / 2] : 0);
+      sz = i < count ? (uint32_t)(wv >> (32 * (u & 1))) : 0u;
+      const uint64_t inc = ss_scan_add(sz, lane);
+      beg = s0w + before + inc - sz;
+      return ss_rl64(inc, 63);
+    };
+    uint64_t total = 0, beg0 = 0;
+    uint32_t sz0 = 0;
+    bool bad = false;
+    for (uint32_t base = 0; base < count; base += 64) {
+      uint32_t sz;
+      uint64_t beg;
+      const uint64_t sum = round(base, total, sz, beg);
+      bad |= __ballot(sz > (uint32_t)kMaxSegmentWords) != 0;  // (a negative size too)
+      if (base == 0) {
+        sz0 = sz;
+        beg0 = beg;
+      }
+      total += sum;
+    }
+    if (bad || total > limit || s0w + total > W) break;
+    // the next message's first words on their way before this one's stores
+    const uint64_t xn = s0w + total;
+    head = xn < W ? out[min(xn + (uint64_t)lane, W - 1)] : 0;
+    uint64_t before = 0;
+    for (uint32_t base = 0; base < count; base += 64) {
+      uint32_t sz = sz0;
+      uint64_t beg = beg0;
+      if (base) before += round(base, before, sz, beg);
+      else before = ss_rl64(beg0 + sz0, 63) - s0w;
+      const uint64_t j = sb + base + (uint32_t)lane;
+      if (base + (uint32_t)lane < count && (int64_t)j < seg_lim) {
+        seg_begin[j] = beg;
+        seg_words[j] = sz;
+      }
+    }
+    x = xn;
+    sb += count;
+    ++m;
+  }
+  if (lane == 0) M.ctl[0] = m + 1;
+}
+
+// boundary T (a word of the flat stream) as a record start: the walk of one
+// PackedInputStream.read that must end exactly there, from the block before
+// it.  CPK_OK and the byte, or what the read throws.
+__device__ int ms_walk(const uint8_t *__restrict__ pk, uint64_t R, const SsBufs &B, uint64_t nb, uint64_t T,
+                       uint64_t &at) {
+  const uint64_t lo = ms_block(B, nb, T);
+  uint64_t p = B.E[lo], w = B.WO[lo];
+  while (w < T) {
+    if (p >= R) return CPK_ETRUNC;
+    const uint64_t room = T - w - 1;  // words the read still takes after this record's first
+    const uint32_t t = pk[p];
+    if (t == 0) {
+      if (p + 2 > R) return CPK_ETRUNC;
+      const uint32_t c = pk[p + 1];
+      if (c > room) return CPK_EOVERRUN;
+      p += 2;
+      w += 1u + c;
+    } else if (t == 0xffu) {
+      if (p + 10 > R) return CPK_ETRUNC;
+      const uint32_t c = pk[p + 9];
+      if (c > room) return CPK_EOVERRUN;
+      if (p + 10 + 8ull * c > R) return CPK_ETRUNC;
+      p += 10 + 8ull * c;
+      w += 1u + c;
+    } else {
+      const uint32_t len = 1u + (uint32_t)__builtin_popcount(t);
+      if (p + len > R) return CPK_ETRUNC;
+      p += len;
+      w += 1;
+    }
+  }
+  at = p;
+  return CPK_OK;
+}
+
+// a wave per entry of the chain: the message read as Serialize.read does it
+__global__ __launch_bounds__(256) void ms_bound_kernel(const uint8_t *__restrict__ pk,
+                                                       const uint64_t *__restrict__ out, uint64_t nbmax, SsBufs B,
+                                                       MsBufs M, uint64_t limit, uint64_t *__restrict__ msg_off,
+                                                       int64_t msg_lim) {
+  if (M.ctl[3] | B.flag[0]) return;
+  const int lane = (int)(threadIdx.x & 63);
+  const uint64_t R = B.lim[0], nb = ss_nb(B, nbmax), W = B.WO[nb];
+  const uint64_t entries = min(M.ctl[0], M.mcap);
+  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64);
+  for (uint64_t m = (uint64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64; m < entries; m += waves) {
+    const uint64_t x = M.X[m];
+    uint64_t p0 = 0, q = 0;
+    int st = ms_walk(pk, R, B, nb, x, p0);  // (its first byte: where the message before it ended)
+    const bool end = st == CPK_OK && x == W && p0 == R;  // the stream ends cleanly in front of it
+    if (st == CPK_OK && !end) {
+      st = ms_walk(pk, R, B, nb, x + 1, q);
+      uint64_t first = 0;
+      uint32_t count = 0, rest = 0;
+      if (st == CPK_OK) {
+        first = out[x];
+        const int32_t raw = (int32_t)(uint32_t)first;
+        if (raw < 0 || raw > 511 || (int32_t)(uint32_t)(first >> 32) < 0) st = CPK_EFRAME;
+        count = (uint32_t)raw + 1;
+        rest = (count & ~1u) / 2;
+      }
+      if (st == CPK_OK && rest) st = ms_walk(pk, R, B, nb, x + 1 + rest, q);
+      const uint64_t s0w = x + 1 + rest;
+      auto size_of = [&](uint32_t i) -> uint32_t {
+        const uint32_t u = i + 1;
+        return i < count ? (uint32_t)(out[x + u / 2] >> (32 * (u & 1))) : 0u;
+      };
+      if (st == CPK_OK) {
+        uint64_t total = 0;
+        bool neg = false;
+        for (uint32_t base = 0; base < count; base += 64) {
+          const uint32_t sz = size_of(base + (uint32_t)lane);
+          neg |= __ballot((int32_t)sz < 0) != 0;
+          total += ss_rl64(ss_scan_add(sz, lane), 63);
+        }
+        if (neg || total > limit) st = CPK_EFRAME;
+      }
+      // the segments in order: one over 2^28 - 1 words fails where it would be
+      // allocated (Serialize.java:45-53), one whose read fails with that status
+      uint64_t before = 0;
+      for (uint32_t base = 0; st == CPK_OK && base < count; base += 64) {
+        const uint32_t i = base + (uint32_t)lane;
+        const uint32_t sz = size_of(i);
+        const uint64_t inc = ss_scan_add(sz, lane);
+        int ls = CPK_OK;
+        if (sz > (uint32_t)kMaxSegmentWords) ls = CPK_EFRAME;
+        else if (sz) ls = ms_walk(pk, R, B, nb, s0w + before + inc, q);
+        const uint64_t failed = __ballot(ls != CPK_OK);
+        if (failed) st = __builtin_amdgcn_readlane(ls, (int)__builtin_ctzll(failed));
+        before += ss_rl64(inc, 63);
+      }
+      // (the chain's last entry is the stream's end or a message that fails)
+      if (st == CPK_OK && m + 1 == M.ctl[0]) st = CPK_EUNSUPPORTED;
+    }
+    if (lane == 0) {
+      M.P[m] = p0;
+      M.ST[m] = st;
+      if (st != CPK_OK) atomicMin((unsigned long long *)&M.ctl[1], (unsigned long long)m);
+      if ((int64_t)m <= msg_lim) msg_off[m] = p0;
+    }
+  }
+}
+
+// row: [0] messages, [1] their segments, [2] their words, [3] bytes consumed,
+// [4] tail status, [5] entries the chain needs, [6] flags, [7] the stream's words
+__global__ void ms_final_kernel(uint64_t nbmax, SsBufs B, MsBufs M) {
+  if (threadIdx.x || blockIdx.x) return;
+  uint64_t *r = M.res;
+  r[7] = B.WO[ss_nb(B, nbmax)];
+  r[6] = M.ctl[3] | (B.flag[0] ? kMsIrregular : 0);
+  if (r[6]) return;
+  const uint64_t entries = M.ctl[0];
+  r[5] = entries;
+  if (entries > M.mcap) {
+    r[6] = kMsShort;
+    return;
+  }
+  const uint64_t nm = min(M.ctl[1], entries - 1);
+  r[0] = nm;
+  r[1] = M.S[nm];
+  r[2] = M.X[nm];
+  r[3] = M.P[nm];
+  r[4] = (uint64_t)(int64_t)M.ST[nm];
 }

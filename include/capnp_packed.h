@@ -250,6 +250,62 @@ int cpk_decode_messages(cpk_ctx ctx, const void *d_packed, const uint64_t *d_msg
 int cpk_read_message(cpk_ctx ctx, const void *d_packed, uint64_t avail, uint64_t traversal_limit_words,
                      void *d_out, uint64_t out_cap_words, uint64_t *d_info, void *stream);
 
+/* A whole stream of packed messages whose boundaries are not known: a log
+ * file, a pipe or a socket buffer that SerializePacked.write was called on
+ * message after message.  The semantics are those of a loop of
+ * SerializePacked.read (SerializePacked.java:51-66, Serialize.java:119-178)
+ * over the first `avail` bytes, until the bytes are used up or a message
+ * fails; the device finds the messages itself, in one call.
+ *   d_packed : 16-byte aligned, readable up to round_up(avail, 16).
+ *   d_out    : 8-byte aligned, out_cap_words words; receives the flat
+ *              unpacked stream: every message's table words followed by its
+ *              segments, in stream order.  The segments are addressed in place:
+ *   d_seg_begin, d_seg_words : uint64[seg_cap], written: segment j's first
+ *              word in d_out and its length, segments numbered over all
+ *              messages in order.
+ *   d_msg_seg_off : uint64[msg_cap + 1], written: message m's segments are
+ *              [d_msg_seg_off[m], d_msg_seg_off[m + 1]).
+ *   d_msg_off : uint64[msg_cap + 1], written: message m's first packed byte;
+ *              d_msg_off[nm] = the bytes consumed.
+ *   h_info   : host, uint64[CPK_MS_INFO_WORDS], written after one
+ *              synchronisation of `stream` (a second only for a stream of
+ *              more than a message per 64 bytes): [0] complete messages nm,
+ *              [1] their segments, [2] their words in d_out, [3] bytes
+ *              consumed (the packed end of the last complete message), [4]
+ *              tail status as int64: CPK_OK iff [3] == avail, else what the
+ *              reference's next read would throw on the bytes from [3] on:
+ *              CPK_ETRUNC, CPK_EFRAME, or CPK_EOVERRUN (a run across a piece
+ *              boundary: first table word / rest of the table / segment /
+ *              next message).
+ * Messages before the first failing one are decoded and reported, nothing
+ * for the failing one or the bytes after it (d_out beyond [2] words and the
+ * arrays beyond the counts are undefined).  Each message is held against
+ * traversal_limit_words on its own.
+ * Returns CPK_OK whenever the call ran (the tail status is in h_info[4]);
+ * CPK_ENOMEM, with nothing guaranteed in the output arrays, when
+ * out_cap_words, msg_cap or seg_cap is too small: h_info[2] is then the
+ * words d_out must hold (the whole stream's), and h_info[0], [1] the
+ * messages and segments, exact whenever out_cap_words was enough -- so two
+ * preliminary calls at most size everything (the arrays may be NULL with a
+ * capacity of 0).  CPK_EINVAL for misaligned or missing pointers.  avail ==
+ * 0: no messages, tail CPK_OK. */
+#define CPK_MS_INFO_WORDS 5
+int cpk_decode_message_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
+                              uint64_t traversal_limit_words,
+                              void *d_out, uint64_t out_cap_words,
+                              uint64_t *d_msg_off, uint64_t *d_msg_seg_off, uint32_t msg_cap,
+                              uint64_t *d_seg_begin, uint64_t *d_seg_words, uint32_t seg_cap,
+                              uint64_t *h_info, void *stream);
+/* The same with every pointer in host memory; synchronous (the bytes staged
+ * through the context's pinned slot, the words and the four arrays copied
+ * back; the same CPK_ENOMEM sizing protocol). */
+int cpk_decode_message_stream_host(cpk_ctx ctx, const void *h_packed, uint64_t avail,
+                                   uint64_t traversal_limit_words,
+                                   void *h_out, uint64_t out_cap_words,
+                                   uint64_t *h_msg_off, uint64_t *h_msg_seg_off, uint32_t msg_cap,
+                                   uint64_t *h_seg_begin, uint64_t *h_seg_words, uint32_t seg_cap,
+                                   uint64_t *h_info);
+
 /* Host-memory convenience forms (the socket/file ByteBuffer path,
  * SerializePacked.java:75-96, :119-134).  Synchronous.  encode_host and
  * decode_host pipeline the batch in chunks of whole pieces through pinned
