@@ -121,7 +121,22 @@ struct SpLay {
   static constexpr int kDefer = ((int)(F::kRing - 16) / 640) & ~1;
   static_assert(F::kRing % 16 == 0, "whole lines");
   static_assert(kSpoRing % 16 == 0 && kScr % 16 == 0, "LDS alignment");
+  // The ring's invariant: the relative lines that hold bytes not yet stored,
+  // [ft, ceil(rel / 16)), are at most kRingLines, so no two of them share a
+  // ring line (two that did would be OR-ed together when the older is stored
+  // and the younger's bytes cleared with it).  sp_b keeps it in three places:
+  //  - a wave whose bytes + 16 fit the ring lays out everything, then stores;
+  //  - any other wave lays out kDefer steps (<= 640 bytes each) from rel = 0,
+  //    fetches its offset and stores every whole group of 64 lines (drain);
+  //  - from then on a pair of steps (<= 2 x 640 bytes) is laid out behind at
+  //    most 63 complete lines and a partial one (< 64 x 16 bytes), and the
+  //    groups of 64 lines it completes are stored before the next pair.
+  // (Until this was asserted the pair after the deferred steps went in
+  // before anything was stored, and a pair's up to 80 lines were followed by
+  // a store of 64: all-nonzero words, 2,050 bytes per 256, passed the sparse
+  // form's 4,096 bytes at the first pair and stayed past it to the wave's end.)
   static_assert(kDefer * 640 + 16 <= (int)F::kRing && kDefer % 2 == 0, "deferred steps must fit the ring");
+  static_assert(64 * 16 + 2 * 640 <= F::kRing, "a pair of steps behind an incomplete group of lines must fit the ring");
   static_assert(kLds * F::kWpe <= 160u * 1024u, "the workgroups per CU must fit its LDS");
 };
 // ring line of relative line i (the dense form's 11 KiB ring is no power of two)
@@ -627,6 +642,17 @@ __device__ __forceinline__ void sp_b(SpRegs<F> &R, int cnt, const uint64_t *lut,
       atomicOr(rp + 3, d3);
     }
   };
+  // complete lines leave 64 at a time (one full-wave store), every group of
+  // 64 there is: fewer than 64 complete lines stay behind (SpLay: the room
+  // the next pair of steps is laid out into)
+  auto drain = [&]() __attribute__((always_inline)) {
+    const uint32_t done = rel >> 4;
+    if (done - ft >= 64u) {
+      wave_lds_order();
+      sp_flush_rel<F>(out, ring, g0, ft, ft + ((done - ft) & ~63u), lane, ocap);
+      wave_lds_order();
+    }
+  };
   // steps j and j + 1 (when j + 1 < cnt): both byte counts in one wave scan
   // (16-bit halves: a step's strings total at most 640 bytes)
   auto step = [&](const int j) __attribute__((always_inline)) {
@@ -661,15 +687,9 @@ __device__ __forceinline__ void sp_b(SpRegs<F> &R, int cnt, const uint64_t *lut,
           put(relb + (incl >> 16) - nb2, b0, b1, b2, nb2, qb % SpLay<F>::kRing4 - qb);
         }
         rel += ta + (stot >> 16);
-        // complete lines leave 64 at a time (one full-wave store)
-        if (known) {
-          const uint32_t done = rel >> 4;
-          if (done - ft >= 64u) {
-            wave_lds_order();
-            sp_flush_rel<F>(out, ring, g0, ft, ft + 64, lane, ocap);
-            wave_lds_order();
-          }
-        }
+        // (marking this unlikely moves the stores' code out of the steps:
+        // config 2 encode -0.5 %, config 4 +1 %, docs/tuning_log.md; dropped)
+        if (known) drain();
       }
     }
 
@@ -683,6 +703,7 @@ __device__ __forceinline__ void sp_b(SpRegs<F> &R, int cnt, const uint64_t *lut,
     g0 = getbase();
     g0 = sp_uni(g0);
     known = true;
+    drain();  // (the deferred steps' lines: the next pair needs their room)
   }
 #pragma unroll
   for (int j = kDefer; j < kSpWS; j += 2)

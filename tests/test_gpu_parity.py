@@ -773,7 +773,8 @@ def _hand_made_units(all_ff):
     """Pieces of 12288 words (two units each): all zero (a zero run covers
     the whole first chunk, so its exit state depends on the entering one),
     all 0xFF bytes when asked for (a literal stretch crosses the unit
-    boundary, every count at its 255 cap), zero except the last word."""
+    boundary, every count at its 255 cap, every wave's output four times the
+    sparse form's ring), zero except the last word."""
     w = [np.zeros(12288, dtype=np.uint64) for _ in range(3)]
     w[1][:] = 0xFFFFFFFFFFFFFFFF
     w[2][-1] = 0x8000000000000001
@@ -801,17 +802,17 @@ def test_both_forms_on_both_densities(form_ctx, oracle, cfg, words, monkeypatch)
 
 
 def test_both_forms_on_whole_chunk_runs(form_ctx, oracle, monkeypatch):
-    """Each form on the hand-made two-unit pieces (_hand_made_units).  The
-    sparse form's batch is without the all-0xFF piece: on that piece it
-    stores zeros for 352 of the piece's 98,400 packed bytes (the first at
-    byte 13,312 of the piece; the offsets are right), alone or next to the
-    other two pieces, while the dense form packs it correctly.  That is how
-    the sparse form behaved before its constants became a template argument,
-    and it is left as found.  (CPK_NO_SMALL: the two remaining pieces would
-    otherwise fit the one-workgroup host path.)"""
+    """Each form on the hand-made two-unit pieces (_hand_made_units): the
+    all-zero piece, the all-0xFF piece and the piece that is zero but for its
+    last word, in one batch, through the dense and the sparse form alike.
+    The all-0xFF piece's waves each emit 16,400 bytes (8,200 in the second
+    unit), several times either ring, so the flush has to keep pace with the
+    layout from the first step after the deferred ones to the wave's last
+    (tests/test_gpu_sp_ring.py sweeps that pressure).  (CPK_NO_SMALL keeps the
+    batch off the one-workgroup host path.)"""
     monkeypatch.setenv("CPK_NO_SMALL", "1")
     c, form = form_ctx
-    data, swo = _hand_made_units(all_ff=form == "d")
+    data, swo = _hand_made_units(all_ff=True)
     _check_batch(c, oracle, data, swo)
 
 
