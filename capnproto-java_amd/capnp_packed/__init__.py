@@ -39,9 +39,11 @@ EXPORTS = [
     "cpk_read_message", "cpk_read_message_host", "cpk_ctx_small_fallbacks",
     "cpk_encode_batch_cap", "cpk_encode_messages_cap", "cpk_ctx_dense_windows",
     "cpk_decode_message_stream", "cpk_decode_message_stream_host",
+    "cpk_encode_message_stream", "cpk_encode_message_stream_host",
 ]
 MSG_HEAD_WORDS, MSG_INFO_WORDS = 257, 517  # CPK_MSG_HEAD_WORDS, CPK_MSG_INFO_WORDS
 MS_INFO_WORDS = 5  # CPK_MS_INFO_WORDS
+EMS_INFO_WORDS = 6  # CPK_EMS_INFO_WORDS
 
 
 class CodecError(RuntimeError):
@@ -111,6 +113,8 @@ def load(path: Path | None = None, strict: bool = True) -> ctypes.CDLL:
         "cpk_read_message_host": ([vp, vp, u64, u64, vp, u64, vp], i32),
         "cpk_decode_message_stream": ([vp, vp, u64, u64, vp, u64, vp, vp, u32, vp, vp, u32, vp, vp], i32),
         "cpk_decode_message_stream_host": ([vp, vp, u64, u64, vp, u64, vp, vp, u32, vp, vp, u32, vp], i32),
+        "cpk_encode_message_stream": ([vp, vp, u64, u64, vp, u64, vp, u32, vp, u32, vp, vp], i32),
+        "cpk_encode_message_stream_host": ([vp, vp, u64, u64, vp, u64, vp, u32, vp, u32, vp], i32),
     }
     for name, (args, res) in sig.items():
         if not strict and not hasattr(L, name):
@@ -542,6 +546,71 @@ def _decode_message_stream_host(self, packed, traversal_limit_words: int = 8 * 1
 
 Context.decode_message_stream = _decode_message_stream
 Context.decode_message_stream_host = _decode_message_stream_host
+
+
+def _encode_message_stream(self, d_in, avail_words: int, d_out, d_out_off, d_msg_piece,
+                           traversal_limit_words: int = 8 * 1024 * 1024, stream=None):
+    """cpk_encode_message_stream: a loop of Serialize.read over a
+    device-resident stream of unpacked messages whose boundaries are not known
+    (what decode_message_stream writes), each message packed as
+    SerializePacked.write packs it.  d_out gets the packed bytes, d_out_off the
+    piece offsets (table, segments; next message), d_msg_piece each message's
+    first piece.  Capacities come from the tensors' sizes (None: 0).
+    -> (rc, info): rc CPK_OK or CPK_ENOMEM (info then holds the sizes needed);
+    info = [messages, pieces, words consumed, packed bytes, tail status,
+    largest piece in words]."""
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+
+    def words(t):
+        return t.numel() * t.element_size() // 8 if t is not None else 0
+    if words(d_out_off) == 0:
+        d_out_off = None
+    if words(d_msg_piece) == 0:
+        d_msg_piece = None
+    out_cap = d_out.numel() * d_out.element_size() if d_out is not None else 0
+    info = np.zeros(EMS_INFO_WORDS, np.uint64)
+    rc = self._lib.cpk_encode_message_stream(
+        self.handle, ptr(d_in), int(avail_words), int(traversal_limit_words), ptr(d_out) if out_cap else None,
+        out_cap, ptr(d_out_off), max(words(d_out_off) - 1, 0), ptr(d_msg_piece), max(words(d_msg_piece) - 1, 0),
+        info.ctypes.data, self._stream(stream))
+    if rc not in (OK, ENOMEM):
+        _check(rc, "cpk_encode_message_stream")
+    out = [int(v) for v in info]
+    out[4] = int(info.view(np.int64)[4])
+    return rc, out
+
+
+def _encode_message_stream_host(self, words_or_bytes, traversal_limit_words: int = 8 * 1024 * 1024):
+    """cpk_encode_message_stream_host -> (tail status, packed bytes, out_off
+    uint64[pieces + 1], msg_piece uint64[messages + 1], words consumed): every
+    complete message of the unpacked stream, packed in order.  Whole words
+    only (trailing bytes short of a word are not part of the stream).  Sized
+    by the CPK_ENOMEM protocol: the arrays first, then the bytes."""
+    if isinstance(words_or_bytes, np.ndarray):
+        w = np.ascontiguousarray(words_or_bytes).view(np.uint8).reshape(-1)
+    else:
+        w = np.frombuffer(bytes(words_or_bytes), np.uint8)
+    nw = w.size // 8
+    w = np.ascontiguousarray(w[: 8 * nw]).view(np.uint64) if nw else np.zeros(1, np.uint64)
+    info = np.zeros(EMS_INFO_WORDS, np.uint64)
+    cap = np_ = nm = 0
+    for _ in range(3):
+        out = np.zeros(max(cap, 1), np.uint8)
+        off, mp = np.zeros(np_ + 1, np.uint64), np.zeros(nm + 1, np.uint64)
+        rc = self._lib.cpk_encode_message_stream_host(
+            self.handle, w.ctypes.data if nw else None, nw, int(traversal_limit_words),
+            out.ctypes.data if cap else None, cap, off.ctypes.data, np_, mp.ctypes.data, nm, info.ctypes.data)
+        if rc != ENOMEM:
+            break
+        cap, np_, nm = max(cap, int(info[3])), max(np_, int(info[1])), max(nm, int(info[0]))
+    _check(rc, "cpk_encode_message_stream_host")
+    return (int(info.view(np.int64)[4]), out[: int(info[3])].tobytes(), off[: int(info[1]) + 1],
+            mp[: int(info[0]) + 1], int(info[2]))
+
+
+Context.encode_message_stream = _encode_message_stream
+Context.encode_message_stream_host = _encode_message_stream_host
 
 
 def gen_params(cfg: int, z: float, lz: float, q: float) -> GenParams:

@@ -499,6 +499,52 @@ struct SerializePacked {
                                uint64_t traversal_limit_words = 8ull << 20) {
     return readAll(gpu, bytes.data(), bytes.size(), traversal_limit_words);
   }
+
+  // The inverse of readAll's pass: a buffer of UNPACKED messages, one after
+  // the other as Serialize.write leaves them (Serialize.java:256-288), read
+  // by a loop of Serialize.read and written with SerializePacked.write, in
+  // ONE GPU pass (cpk_encode_message_stream_host): the device finds the
+  // messages itself.  `packed` holds every complete message in front of the
+  // first that fails, msg_off[m] message m's first packed byte (the last
+  // entry the total); `consumed` is where the last of them ends in the input,
+  // in bytes, `tail` CPK_OK when that is the end of the whole words, else
+  // what the next Serialize.read would throw.
+  struct PackAllResult {
+    std::vector<uint8_t> packed;
+    std::vector<uint64_t> msg_off;
+    uint64_t consumed = 0;
+    int tail = CPK_OK;
+  };
+  static PackAllResult packAll(Gpu &gpu, const uint8_t *bytes, size_t size,
+                               uint64_t traversal_limit_words = 8ull << 20) {
+    uint64_t info[CPK_EMS_INFO_WORDS] = {0, 0, 0, 0, 0, 0};
+    // (whole words, 8-byte aligned for the staging copy's sake)
+    std::vector<uint64_t> words(size / 8), off(1), mp(1);
+    if (!words.empty()) std::memcpy(words.data(), bytes, 8 * words.size());
+    PackAllResult res;
+    int rc = CPK_ENOMEM;
+    // sized by the call itself: the arrays first, then the bytes
+    for (int pass = 0; pass < 3 && rc == CPK_ENOMEM; ++pass) {
+      rc = cpk_encode_message_stream_host(gpu.get(), words.data(), words.size(), traversal_limit_words,
+                                          res.packed.empty() ? nullptr : res.packed.data(), res.packed.size(),
+                                          off.data(), (uint32_t)off.size() - 1, mp.data(), (uint32_t)mp.size() - 1,
+                                          info);
+      if (rc != CPK_ENOMEM) break;
+      if (info[1] + 1 > off.size()) off.resize(info[1] + 1);
+      if (info[0] + 1 > mp.size()) mp.resize(info[0] + 1);
+      if (info[3] > res.packed.size()) res.packed.resize(info[3]);
+    }
+    check(rc, "SerializePacked.packAll");
+    res.packed.resize(info[3]);
+    res.consumed = 8 * info[2];
+    res.tail = (int)(int64_t)info[4];
+    for (uint64_t m = 0; m <= info[0]; ++m) res.msg_off.push_back(off[mp[m]]);
+    return res;
+  }
+  static PackAllResult packAll(Gpu &gpu, const std::vector<uint8_t> &bytes,
+                               uint64_t traversal_limit_words = 8ull << 20) {
+    return packAll(gpu, bytes.data(), bytes.size(), traversal_limit_words);
+  }
 };
 
 }  // namespace capnp_amd

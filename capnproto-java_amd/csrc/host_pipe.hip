@@ -1022,4 +1022,50 @@ int cpk_decode_message_stream_host(cpk_ctx ctx, const void *h_packed, uint64_t a
   return CPK_OK;
 }
 
+// A whole stream of unpacked messages from host memory
+// (cpk_encode_message_stream): the words staged whole through the pinned
+// slot 0, the device call, then the packed bytes and the two arrays copied
+// back.  Not pipelined in chunks: the copies and the kernels run one after
+// the other.
+int cpk_encode_message_stream_host(cpk_ctx ctx, const void *h_in, uint64_t avail_words,
+                                   uint64_t traversal_limit_words, void *h_out, uint64_t out_cap,
+                                   uint64_t *h_out_off, uint32_t piece_cap, uint64_t *h_msg_piece, uint32_t msg_cap,
+                                   uint64_t *h_info) {
+  if (!ctx || !h_info || (avail_words && !h_in) || (out_cap && !h_out)) return CPK_EINVAL;
+  if ((piece_cap && !h_out_off) || (msg_cap && !h_msg_piece)) return CPK_EINVAL;
+  if (avail_words > (~0ull >> 4)) return CPK_EINVAL;
+  for (int i = 0; i < CPK_EMS_INFO_WORDS; ++i) h_info[i] = 0;
+  if (avail_words == 0) {
+    if (h_out_off) h_out_off[0] = 0;
+    if (h_msg_piece) h_msg_piece[0] = 0;
+    return CPK_OK;
+  }
+  DeviceGuard g(ctx->device);
+  // meta: out_off [piece_cap + 1] | msg_piece [msg_cap + 1]
+  const uint64_t pc = h_out_off ? piece_cap + 1ull : 0, mc = h_msg_piece ? msg_cap + 1ull : 0;
+  HostPipe *p = nullptr;
+  int rc = pipe_get(ctx, avail_words * 8, out_cap, pc + mc + 1, &p, 1);
+  if (rc) return rc;
+  HostSlot &sl = p->slot[0];
+  uint64_t *m = sl.pin_meta, *dm = sl.d_meta;
+  if (h2d_pipelined(sl.d_in, sl.pin_in, h_in, avail_words * 8, p->sk)) return CPK_EDEVICE;
+  rc = cpk_encode_message_stream(ctx, sl.d_in, avail_words, traversal_limit_words, out_cap ? sl.d_out : nullptr,
+                                 out_cap, pc ? dm : nullptr, pc ? piece_cap : 0, mc ? dm + pc : nullptr,
+                                 mc ? msg_cap : 0, h_info, p->sk);
+  if (rc) {
+    pipe_drain(p);
+    return rc;
+  }
+  const uint64_t nm = h_info[0], np = h_info[1], bytes = h_info[3];
+  if (hipMemcpyAsync(m, dm, (pc + mc) * 8ull, hipMemcpyDeviceToHost, p->sk)) return CPK_EDEVICE;
+  if (bytes) {
+    if (d2h_pipelined(h_out, sl.pin_out, sl.d_out, bytes, p->sk, sl.eh, sl.ed)) return CPK_EDEVICE;
+  } else if (hipStreamSynchronize(p->sk)) {
+    return CPK_EDEVICE;
+  }
+  if (pc) memcpy(h_out_off, m, (np + 1) * 8);
+  if (mc) memcpy(h_msg_piece, m + pc, (nm + 1) * 8);
+  return CPK_OK;
+}
+
 }  // extern "C"

@@ -1604,6 +1604,7 @@ __global__ void gather8_kernel(Gather8 g, uint32_t k, uint64_t *out) {
 #include "encode_sp3.hip"
 #include "decode_v2.hip"
 #include "stream_split.hip"
+#include "encode_ms.hip"
 
 }  // namespace cpk
 
@@ -1631,6 +1632,8 @@ struct cpk_ctx_s {
   uint64_t ss_cap;        //   u64 entries
   uint64_t *ms_buf;       // cpk_decode_message_stream: the frame chain's entries and result row (lazy)
   uint64_t ms_cap;        //   entries (messages)
+  uint64_t *ems_buf;      // cpk_encode_message_stream: the result row | the pieces' word offsets (lazy)
+  uint64_t ems_cap;       //   offsets
   uint64_t *rm_buf;       // cpk_read_message: piece word offsets | piece ends | statuses (lazy)
   uint64_t *fl_buf;       // cpk_decode_batch of a few large pieces: boundaries found [33] (lazy)
   uint64_t *probe_pin;    // host read-backs of a few device words (read_words): pinned [8] (lazy)
@@ -1872,6 +1875,7 @@ void cpk_ctx_destroy(cpk_ctx ctx) {
   if (ctx->sp_desc) hipFree(ctx->sp_desc);
   if (ctx->ss_buf) hipFree(ctx->ss_buf);
   if (ctx->ms_buf) hipFree(ctx->ms_buf);
+  if (ctx->ems_buf) hipFree(ctx->ems_buf);
   if (ctx->rm_buf) hipFree(ctx->rm_buf);
   if (ctx->fl_buf) hipFree(ctx->fl_buf);
   if (ctx->probe_pin) hipHostFree(ctx->probe_pin);
@@ -2593,6 +2597,82 @@ int cpk_decode_message_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
   h_info[2] = r[2];
   h_info[3] = r[3];
   h_info[4] = r[4];
+  return CPK_OK;
+}
+
+// A whole stream of unpacked messages packed (encode_ms.hip): the frame
+// chain over the words, its result row read back (the piece count sizes the
+// encoders' launches), the pieces through cpk_encode_batch_cap, then the
+// packed total and the context's error word read back.
+int cpk_encode_message_stream(cpk_ctx ctx, const void *d_in, uint64_t avail_words, uint64_t traversal_limit_words,
+                              void *d_out, uint64_t out_cap, uint64_t *d_out_off, uint32_t piece_cap,
+                              uint64_t *d_msg_piece, uint32_t msg_cap, uint64_t *h_info, void *stream) {
+  using namespace cpk;
+  if (!ctx || !h_info || (avail_words && !d_in) || (out_cap && !d_out)) return CPK_EINVAL;
+  if (((uintptr_t)d_in & 7) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_out_off & 7) || ((uintptr_t)d_msg_piece & 7))
+    return CPK_EINVAL;
+  if ((piece_cap && !d_out_off) || (msg_cap && !d_msg_piece)) return CPK_EINVAL;
+  for (int i = 0; i < CPK_EMS_INFO_WORDS; ++i) h_info[i] = 0;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (avail_words == 0) {
+    if ((d_out_off && hipMemsetAsync(d_out_off, 0, 8, s) != hipSuccess) ||
+        (d_msg_piece && hipMemsetAsync(d_msg_piece, 0, 8, s) != hipSuccess))
+      return CPK_EDEVICE;
+    return CPK_OK;
+  }
+  // (the last entry each array holds; none without an array.  A message of
+  // `count` segments is 1 + count pieces in at least 1 + count / 2 words:
+  // at most two pieces per word)
+  const int64_t msg_lim = d_msg_piece ? (int64_t)msg_cap : -1;
+  const uint64_t pmax = avail_words > 0x7fffffffull ? 0xffffffffull : 2 * avail_words;
+  const int64_t piece_lim = d_out_off ? (int64_t)(piece_cap < pmax ? piece_cap : pmax) : -1;
+  const uint64_t offs = (uint64_t)(piece_lim + 1);
+  if (!ctx->ems_buf || offs > ctx->ems_cap) {
+    if (ctx->ems_buf) hipFree(ctx->ems_buf);
+    ctx->ems_buf = nullptr;
+    ctx->ems_cap = 0;
+    const uint64_t cap = offs < 1024 ? 1024 : offs + offs / 4;
+    if (hipMalloc(&ctx->ems_buf, (kEmsRow + cap) * 8) != hipSuccess) return CPK_ENOMEM;
+    ctx->ems_cap = cap;
+  }
+  uint64_t *row = ctx->ems_buf, *poff = ctx->ems_buf + kEmsRow;
+  const uint64_t *errw = reinterpret_cast<const uint64_t *>(ctx->tickets + kTkErr);  // (the low half)
+  hipLaunchKernelGGL(ems_chain_kernel, dim3(1), dim3(64), 0, s, (const uint64_t *)d_in, avail_words,
+                     traversal_limit_words, poff, piece_lim, d_msg_piece, msg_lim, row);
+  if (hipGetLastError() != hipSuccess) return CPK_EDEVICE;
+  uint64_t r[6];
+  if (int rc = read_words(ctx, s, {row + kEmsMsgs, row + kEmsPieces, row + kEmsWords, row + kEmsTail,
+                                   row + kEmsMax, errw}, r))
+    return rc;
+  const uint32_t err0 = (uint32_t)r[5];  // (what earlier encodes left for cpk_ctx_take_error)
+  h_info[0] = r[0];
+  h_info[1] = r[1];
+  if ((int64_t)r[0] > msg_lim || (int64_t)r[1] > piece_lim) return CPK_ENOMEM;
+  h_info[2] = r[2];
+  h_info[4] = r[3];
+  h_info[5] = r[4];
+  const uint32_t n = (uint32_t)r[1];
+  if (n == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
+  // (every piece of a complete message is under 2^28 words and the tables
+  // are not empty: the largest piece is a bound the batch call takes)
+  if (int rc = cpk_encode_batch_cap(ctx, d_in, poff, n, r[4], d_out, out_cap, d_out_off, stream)) return rc;
+  // the packed total: the encoders write the last offset whatever the
+  // capacity (the scans; the single pass's look-back); the capacity verdict
+  // follows from it, and the error word tells a wait that timed out
+  uint64_t e[2];
+  if (int rc = read_words(ctx, s, {d_out_off + n, errw}, e)) return rc;
+  h_info[3] = e[0];
+  const uint32_t err1 = (uint32_t)e[1];
+  if ((err1 & ~err0) & (kErrWait | kErrHint)) return CPK_EDEVICE;
+  if (e[0] > out_cap) {
+    // (reported by the return value: the bit the encoders set for it is
+    // taken back unless an earlier call's is still waiting to be taken)
+    if (!(err0 & kErrCap) && hipMemsetD32Async((hipDeviceptr_t)(ctx->tickets + kTkErr), (int)(err1 & ~kErrCap), 1, s) !=
+                                 hipSuccess)
+      return CPK_EDEVICE;
+    return CPK_ENOMEM;
+  }
   return CPK_OK;
 }
 }  // extern "C"

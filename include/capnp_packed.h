@@ -306,6 +306,80 @@ int cpk_decode_message_stream_host(cpk_ctx ctx, const void *h_packed, uint64_t a
                                    uint64_t *h_seg_begin, uint64_t *h_seg_words, uint32_t seg_cap,
                                    uint64_t *h_info);
 
+/* The other direction: a whole stream of UNPACKED messages whose boundaries
+ * are not known -- a file or a socket buffer that Serialize.write was called
+ * on message after message (Serialize.java:256-288), or the flat output of
+ * cpk_decode_message_stream, data words edited in place -- packed in one
+ * call.  The semantics are those of a loop of
+ * Serialize.read(ReadableByteChannel) (Serialize.java:119-178) over the first
+ * `avail_words` words, each message read then written with
+ * SerializePacked.write (SerializePacked.java:101-134): one piece for the
+ * message's segment table, all of its words in one write(), and one per
+ * segment (a segment of 0 words packs to 0 bytes), every piece from fresh run
+ * state, packed back to back in stream order.  The pieces of the complete
+ * messages tile the input words exactly.  The device finds the messages
+ * itself (one wave follows the tables), so the host never learns a boundary.
+ *   d_in     : 8-byte aligned, avail_words words.
+ *   d_out    : 16-byte aligned, out_cap bytes; as in the *_cap forms no byte
+ *              at or past d_out + out_cap is ever stored.
+ *   d_out_off : uint64[piece_cap + 1], written: packed piece offsets in
+ *              stream order (table, segments; next message); the last entry
+ *              is the total.
+ *   d_msg_piece : uint64[msg_cap + 1], written: message m's pieces are
+ *              [d_msg_piece[m], d_msg_piece[m + 1]), so its packed bytes
+ *              start at d_out_off[d_msg_piece[m]].
+ *   h_info   : host, uint64[CPK_EMS_INFO_WORDS], written: [0] complete
+ *              messages, [1] their pieces (messages + segments), [2] words
+ *              consumed (the end of the last complete message), [3] packed
+ *              bytes: the exact total, also when out_cap was too small, [4]
+ *              tail status as int64, [5] the largest piece in words.
+ * Tail status: CPK_OK iff every word was consumed; CPK_ETRUNC when the words
+ * end inside a message (after the first table word when the rest of the
+ * table is due, inside the rest of the table, inside a segment); CPK_EFRAME
+ * for a table Serialize.read refuses, the checks in its order: a count over
+ * 512, a negative size, a total over traversal_limit_words, a segment over
+ * 2^28-1 words.  Each message is held against the limit on its own.
+ * Messages before the first failing one are packed and reported, nothing for
+ * the failing one or the words after it.
+ * Divergence from the reference: the table is packed as its words stand in
+ * the input.  Serialize.write zeroes the pad half-word of an even-count
+ * table and Serialize.read ignores it, so the output equals the reference's
+ * read followed by write exactly when the pad is zero -- every stream a
+ * conforming writer made.  A nonzero pad is kept: the call is lossless,
+ * decoding its output gives the input words back.
+ * Returns CPK_OK whenever the call ran (the tail status is in h_info[4]);
+ * CPK_ENOMEM, with nothing guaranteed in the outputs, when piece_cap, msg_cap
+ * or out_cap is too small: h_info[0] and [1] are then exact and say what the
+ * arrays need, and [3] is exact whenever the arrays were large enough.  The
+ * arrays and d_out may be NULL with a capacity of 0, so two preliminary
+ * calls at most size everything: the first with everything NULL / 0 gives
+ * [0] and [1]; the second with the arrays and out_cap 0 gives [3].
+ * CPK_EINVAL for misaligned or missing pointers.  avail_words == 0: no
+ * messages, tail CPK_OK, d_out_off[0] = 0.
+ * The call synchronises `stream` twice: once after the chain (the piece
+ * count sizes the encoders' launches; a call whose arrays are too small
+ * returns here) and once after the encoders, for [3] and the capacity
+ * verdict.  A capacity overrun is reported by the return value and leaves
+ * nothing behind for cpk_ctx_take_error. */
+#define CPK_EMS_INFO_WORDS 6
+int cpk_encode_message_stream(cpk_ctx ctx, const void *d_in, uint64_t avail_words,
+                              uint64_t traversal_limit_words,
+                              void *d_out, uint64_t out_cap,
+                              uint64_t *d_out_off, uint32_t piece_cap,
+                              uint64_t *d_msg_piece, uint32_t msg_cap,
+                              uint64_t *h_info, void *stream);
+/* The same with every pointer in host memory; synchronous (the words staged
+ * whole through the context's pinned slot, the packed bytes and the two
+ * arrays copied back; the same CPK_ENOMEM sizing protocol).  It does not
+ * pipeline the stream in chunks: copy in, pack, copy out, one after the
+ * other. */
+int cpk_encode_message_stream_host(cpk_ctx ctx, const void *h_in, uint64_t avail_words,
+                                   uint64_t traversal_limit_words,
+                                   void *h_out, uint64_t out_cap,
+                                   uint64_t *h_out_off, uint32_t piece_cap,
+                                   uint64_t *h_msg_piece, uint32_t msg_cap,
+                                   uint64_t *h_info);
+
 /* Host-memory convenience forms (the socket/file ByteBuffer path,
  * SerializePacked.java:75-96, :119-134).  Synchronous.  encode_host and
  * decode_host pipeline the batch in chunks of whole pieces through pinned
