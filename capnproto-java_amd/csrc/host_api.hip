@@ -1,0 +1,1339 @@
+// host_api.hip -- the host layer: the context and its scratch buffers, the
+// launch helpers and the C ABI (include/capnp_packed.h).  Included last by
+// packed_codec.hip, after every kernel: one translation unit.
+
+// ================================================================ C ABI
+struct HostPipe;  // host_pipe.hip: staging of the host-memory forms
+
+// A device buffer of the context, allocated on first use (valid when zeroed:
+// the context is calloc'ed).  reserve() grows one on demand, reserve_fixed()
+// allocates one of a fixed size; cpk_ctx_destroy frees the ones its list names.
+struct DevBuf {
+  uint64_t *p;
+  uint64_t cap;  // entries (reserve); unused by the fixed-size ones
+};
+
+struct cpk_ctx_s {
+  int device;
+  int cus;
+  DevBuf status;          // look-back words
+  uint32_t *tickets;      // cpk::kTkWords words: per-XCD counters, plan ticket, error bits
+  int encoder;            // 0: single pass (encode_sp.hip); 4: size + emit passes; 5: by piece size
+  int sp_form;            // the single pass's form: 0 by density, 1 dense, 2 sparse (CPK_SP_FORM)
+  int decoder;            // 2: record index (decode_v2.hip); 1: block map (decode_kernel); 3: by density
+  DevBuf sp_status;       // single pass: look-back word per piece
+  uint32_t sp_epoch;      //   launch epoch tagging the look-back words, 1..65535
+  DevBuf sp_desc;         //   message batches: piece descriptors | segment tables
+  DevBuf e4_bv;           // encoder v4: per 64-word step its run boundaries, members, heads (kE4RowBytes each)
+  HostPipe *pipe;         // cpk_encode_host / cpk_decode_host staging (lazy)
+  DevBuf ss_buf;          // parallel stream decode scratch (stream_split.hip)
+  DevBuf ms_buf;          // cpk_decode_message_stream: the frame chain's entries (messages) and result row
+  DevBuf ems_buf;         // cpk_encode_message_stream: the result row | the pieces' word offsets
+  DevBuf rm_buf;          // cpk_read_message: piece word offsets | piece ends | statuses (fixed size)
+  DevBuf fl_buf;          // cpk_decode_batch of a few large pieces: boundaries found [33] (fixed size)
+  uint64_t *probe_pin;    // host read-backs of a few device words (read_words): pinned [8] (lazy)
+  DevBuf rm_copy;         // cpk_read_message_host, one-wave path: the packed bytes on the device (fixed size)
+  uint64_t small_seq;     // the one-launch host paths' completion flag values (small_wait)
+  uint64_t small_fallbacks;  // small_wait calls whose flag was unset even after a stream sync (lost flags)
+  uint64_t small_timeouts;   // small_wait calls that waited past 5 ms (late launches included)
+  DevBuf sp_units;        // single pass, pieces over one chunk: unit counts | starts | block sums | unit table
+  // CPK_HOST_TRACE=1 (read at creation): host wall time of the one-message
+  // host paths (cpk_encode_host[_gather], cpk_read_message_host) by phase,
+  // summed per context and printed to stderr by cpk_ctx_destroy
+  uint64_t rm_mw_max;     // cpk_read_message[_host]: streams under it by one workgroup (<= kRmMwMax)
+  int e4_order;           // cpk_encode_messages' two passes, segments largest first: 1 both passes,
+                          // 2 the emit pass only, 0 neither (CPK_E4_ORDER)
+  bool trace;
+  double tr_us[8];
+  uint64_t tr_n[8];
+};
+// the phases (write: staging in, enqueues, waits, staging out; read: same)
+enum { kTrWIn, kTrWLaunch, kTrWWait, kTrWOut, kTrRIn, kTrRLaunch, kTrRWait, kTrROut };
+struct TrClock {
+  cpk_ctx c;
+  std::chrono::steady_clock::time_point t;
+  explicit TrClock(cpk_ctx ctx) : c(ctx) {
+    if (c->trace) t = std::chrono::steady_clock::now();
+  }
+  void mark(int k) {
+    if (!c->trace) return;
+    const auto n = std::chrono::steady_clock::now();
+    c->tr_us[k] += std::chrono::duration<double, std::micro>(n - t).count();
+    ++c->tr_n[k];
+    t = n;
+  }
+};
+
+namespace {
+int hip_ok(hipError_t e) { return e == hipSuccess ? CPK_OK : CPK_EDEVICE; }
+
+struct DeviceGuard {
+  int prev;
+  explicit DeviceGuard(int d) {
+    hipGetDevice(&prev);
+    if (prev != d) hipSetDevice(d);
+  }
+  ~DeviceGuard() {
+    int cur;
+    hipGetDevice(&cur);
+    if (cur != prev) hipSetDevice(prev);
+  }
+};
+
+// order[0..n) = 0..n-1 by size class, largest first (cpk::ord_*); hist:
+// kOrdClasses u32 of scratch
+void ord_launch(const uint64_t *words, uint32_t n, uint32_t *hist, uint32_t *order, hipStream_t s,
+                const uint64_t *swo = nullptr) {
+  const unsigned tb = 256, tg = (n + tb - 1) / tb;
+  (void)hipMemsetAsync(hist, 0, 4 * cpk::kOrdClasses, s);
+  hipLaunchKernelGGL(cpk::ord_hist_kernel, dim3(tg), dim3(tb), 0, s, words, n, hist, swo);
+  hipLaunchKernelGGL(cpk::ord_scan_kernel, dim3(1), dim3(64), 0, s, hist);
+  hipLaunchKernelGGL(cpk::ord_scatter_kernel, dim3(tg), dim3(tb), 0, s, words, n, hist, order, swo);
+}
+
+// out[0..n] = the exclusive scan of in[0..n), out[n] the total (in may be
+// out: each thread reads its entries before it writes them); bsum:
+// scan_blocks(n) words of scratch
+uint32_t scan_blocks(uint64_t n) { return (uint32_t)((n + cpk::kE4ScanBlock - 1) / cpk::kE4ScanBlock); }
+void scan_launch(const uint64_t *in, uint32_t n, uint64_t *bsum, uint64_t *out, hipStream_t s) {
+  const uint32_t nb = scan_blocks(n);
+  hipLaunchKernelGGL(cpk::e4_scan_reduce, dim3(nb), dim3(cpk::kE4ScanThreads), 0, s, in, n, bsum);
+  hipLaunchKernelGGL(cpk::e4_scan_top, dim3(1), dim3(cpk::kE4ScanThreads), 0, s, bsum, nb);
+  hipLaunchKernelGGL(cpk::e4_scan_down, dim3(nb), dim3(cpk::kE4ScanThreads), 0, s, in, n, (const uint64_t *)bsum,
+                     out);
+}
+
+// the decoders' ticket counters (one per XCD) back to zero
+hipError_t dec_tickets_reset(cpk_ctx ctx, hipStream_t s) {
+  return hipMemsetAsync(ctx->tickets + cpk::kTkDec, 0, 8 * cpk::kTkStride * 4, s);
+}
+
+// the two passes' grid: persistent blocks of kE4Waves waves, a wave per piece
+unsigned e4_grid(cpk_ctx ctx, uint32_t n) {
+  const unsigned grid = (unsigned)(8 * ctx->cus), want = (n + cpk::kE4Waves - 1) / cpk::kE4Waves;
+  return grid > want ? want : grid;
+}
+
+// The front half of the block map over `reach` bytes in nb blocks
+// (stream_split.hip): every block's walks, the groups' and the stream's
+// chains, the blocks' first records.  swo / n: the stream's pieces, where the
+// caller knows them.
+int ss_map_launch(cpk_ctx ctx, const uint8_t *pk, uint64_t reach, const uint64_t *swo, uint32_t n, uint64_t nb,
+                  const cpk::SsBufs &B, hipStream_t s) {
+  using namespace cpk;
+  const uint64_t ng = (nb + kSsGroup - 1) / kSsGroup;
+  if (hipMemsetAsync(B.N2, 0, 4 * nb, s) != hipSuccess || hipMemsetAsync(B.flag, 0, 8, s) != hipSuccess ||
+      dec_tickets_reset(ctx, s) != hipSuccess)
+    return CPK_EDEVICE;
+  const unsigned tb = 256, gb = (unsigned)((nb + tb - 1) / tb);
+  hipLaunchKernelGGL(ss_scan_kernel, dim3((unsigned)ng), dim3(kSsThreads), kSsLds, s, pk, reach, swo, n, nb, B);
+  hipLaunchKernelGGL(ss_group_kernel, dim3((unsigned)ng), dim3(64), 0, s, pk, nb, B);
+  hipLaunchKernelGGL(ss_top_kernel, dim3(1), dim3(64), 0, s, pk, nb, B);
+  hipLaunchKernelGGL(ss_cut_kernel, dim3(gb), dim3(tb), 0, s, nb, B);
+  return CPK_OK;
+}
+
+// Room for `need` entries in b: a new allocation of max(floor, need + need / 4)
+// entries when it has fewer, of bytes(entries) bytes (8 each when null).
+// *grew tells the caller that the buffer is new (its contents undefined).
+// After a failed allocation the buffer is empty: p null, cap 0.
+int reserve(DevBuf &b, uint64_t need, uint64_t floor = 0, uint64_t (*bytes)(uint64_t) = nullptr,
+            bool *grew = nullptr) {
+  if (b.p && need <= b.cap) return CPK_OK;
+  if (b.p) hipFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+  const uint64_t cap = need < floor ? floor : need + need / 4;
+  if (hipMalloc(&b.p, bytes ? bytes(cap) : cap * 8) != hipSuccess) {
+    b.p = nullptr;
+    return CPK_ENOMEM;
+  }
+  b.cap = cap;
+  if (grew) *grew = true;
+  return CPK_OK;
+}
+// a buffer of a fixed size, allocated by the first call
+int reserve_fixed(DevBuf &b, uint64_t bytes) {
+  if (b.p || hipMalloc(&b.p, bytes) == hipSuccess) return CPK_OK;
+  b.p = nullptr;
+  return CPK_ENOMEM;
+}
+}  // namespace
+
+static int decode_batch_impl(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off, const uint64_t *d_swo,
+                             uint32_t n, void *d_out, int32_t *d_status, void *stream, bool probe);
+
+// The end of a one-launch small path (rm_small_kernel, sp_small_kernel):
+// its kernel writes seq to *flag (pinned host memory) after all its other
+// writes, so the host reads its results once the flag turns -- without the
+// stream synchronisation's wait for the kernel's completion signal.  Past a
+// bound (the kernel is slow or faulted) the stream synchronisation decides.
+// Returns 0 or nonzero like hipStreamSynchronize.
+// The flag word is cleared by small_arm before the launch (it is pinned
+// memory other calls use for other data) and its values carry a tag no
+// offset or size the slot held can equal.
+constexpr uint64_t kSmallTag = 0x5ea1ull << 48;
+static uint64_t small_arm(cpk_ctx ctx, uint64_t *flag) {
+  __atomic_store_n(flag, 0ull, __ATOMIC_RELEASE);
+  return kSmallTag | (++ctx->small_seq & ((1ull << 48) - 1));
+}
+static int small_wait(cpk_ctx ctx, hipStream_t s, const uint64_t *flag, uint64_t seq) {
+  const auto t0 = std::chrono::steady_clock::now();
+  for (uint32_t i = 1;; ++i) {
+    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return 0;
+    __builtin_ia32_pause();
+    if ((i & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
+  }
+  // A late launch (a busy GPU, queueing behind other streams, the first
+  // module load) also gets here: the stream synchronisation decides.  Only a
+  // flag still unset after it -- a kernel that completed without writing it,
+  // a device-side bug -- is counted (cpk_ctx_small_fallbacks); a lost flag
+  // would otherwise only cost 5 ms per call and pass every test.
+  ++ctx->small_timeouts;
+  if (hipStreamSynchronize(s) != hipSuccess) return 1;
+  if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return 0;
+  ++ctx->small_fallbacks;
+  return 1;
+}
+#include "host_pipe.hip"
+
+extern "C" {
+
+int cpk_abi_version(void) { return CPK_ABI_VERSION; }
+
+#ifdef CPK_PHASE_STATS
+// diagnostic builds only: read and clear the per-phase cycle sums
+int cpk_debug_phase_stats(unsigned long long *host64) {
+  if (hipMemcpyFromSymbol(host64, HIP_SYMBOL(cpk::g_phase), 64 * 8) != hipSuccess) return CPK_EDEVICE;
+  unsigned long long z[64] = {0};
+  return hipMemcpyToSymbol(HIP_SYMBOL(cpk::g_phase), z, sizeof z) == hipSuccess ? CPK_OK : CPK_EDEVICE;
+}
+#endif
+
+const char *cpk_status_string(int s) {
+  switch (s) {
+    case CPK_OK: return "ok";
+    case CPK_EINVAL: return "invalid argument / misaligned piece";
+    case CPK_ETRUNC: return "premature end of packed input";
+    case CPK_EOVERRUN: return "packed run past the end of the piece";
+    case CPK_ETRAILING: return "piece filled before the end of its packed bytes";
+    case CPK_EFRAME: return "invalid segment table";
+    case CPK_ENOMEM: return "out of device memory";
+    case CPK_EDEVICE: return "HIP runtime error";
+    case CPK_EUNSUPPORTED: return "piece not supported by this build";
+    default: return "unknown status";
+  }
+}
+
+uint64_t cpk_packed_bound(uint64_t words) { return 8 * words + 2 * ((words + 1) / 2); }
+
+uint64_t cpk_batch_packed_capacity(const uint64_t *h_swo, uint32_t n) {
+  uint64_t s = 0;
+  for (uint32_t i = 0; i < n; ++i) s += cpk_packed_bound(h_swo[i + 1] - h_swo[i]);
+  return s + 16;
+}
+
+int cpk_ctx_create(int device, cpk_ctx *out) {
+  if (!out) return CPK_EINVAL;
+  *out = nullptr;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
+    return CPK_EDEVICE;
+  DeviceGuard g(device);
+  cpk_ctx c = (cpk_ctx)calloc(1, sizeof(cpk_ctx_s));
+  if (!c) return CPK_ENOMEM;
+  c->device = device;
+  {
+    // Encoders: the single pass (encode_sp.hip) for batches of like-sized
+    // pieces of 4 Ki words and more (3.65 against 5.06 ms per 131,072
+    // config-2 pieces of 8 Ki words; 3.96 against 5.50 ms for 16,384 of
+    // 64 Ki words), the two passes (encode_v4.hip) for mixed sizes and
+    // message batches; chosen on the device (e4_gate_kernel) among the
+    // batches sp_takes admits.  CPK_ENCODER=0 / 4 force one of them.
+    const char *e = getenv("CPK_ENCODER");
+    c->encoder = (e && e[0] == '4') ? 4 : (e && e[0] == '0') ? 0 : 5;
+    // CPK_SP_FORM=dense / sparse forces the single pass's form where the
+    // gate picks the single pass (A/B of the density threshold)
+    const char *f = getenv("CPK_SP_FORM");
+    c->sp_form = (f && f[0] == 'd') ? 1 : (f && f[0] == 's') ? 2 : 0;
+    // CPK_DECODER=1 selects the block-map decoder, 2 the record-index one
+    const char *d = getenv("CPK_DECODER");
+    c->decoder = (d && d[0] == '2') ? 2 : (d && d[0] == '1') ? 1 : 3;
+    const char *t = getenv("CPK_HOST_TRACE");
+    c->trace = t && t[0] == '1';
+    // (CPK_RM_MW_MAX_KB: A/B of the one-workgroup reader's upper bound)
+    const char *m = getenv("CPK_RM_MW_MAX_KB");
+    c->rm_mw_max = m ? (uint64_t)atoll(m) << 10 : 0;
+    const char *o = getenv("CPK_E4_ORDER");
+    c->e4_order = o ? atoi(o) : 1;
+  }
+  if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
+    c->cus = 256;
+  if (hipMalloc(&c->tickets, cpk::kTkWords * 4) != hipSuccess ||
+      hipMemset(c->tickets, 0, cpk::kTkWords * 4) != hipSuccess) {
+    free(c);
+    return CPK_ENOMEM;
+  }
+  // the kernels' dynamic LDS, above the 64 KiB default for some: set here,
+  // with the context's device current (the attribute is per device).  The
+  // library is built for gfx950 only (160 KiB of LDS per CU): each request
+  // is checked against that at compile time, so a refused attribute is a
+  // runtime/driver failure, reported as CPK_EDEVICE
+  constexpr uint32_t kGfx950Lds = 160 * 1024;
+  static_assert(cpk::kDecLds <= kGfx950Lds && cpk::SpLay<cpk::SpDense>::kLds <= kGfx950Lds &&
+                    cpk::kSpSmallLds <= kGfx950Lds && cpk::kMwLds <= kGfx950Lds && cpk::kSsLds <= kGfx950Lds,
+                "a kernel's dynamic LDS exceeds gfx950's 160 KiB");
+  const struct {
+    const void *f;
+    uint32_t bytes;
+  } lds[] = {{(const void *)cpk::decode_kernel<false>, cpk::kDecLds},
+             {(const void *)cpk::decode_kernel<true>, cpk::kDecLds},
+             {(const void *)cpk::decode_kernel<false, true>, cpk::kDecLds},
+             {(const void *)cpk::decode_kernel<true, true>, cpk::kDecLds},
+             {(const void *)cpk::sp_encode_kernel<true>, cpk::SpLay<cpk::SpDense>::kLds},
+             {(const void *)cpk::sp_encode_kernel<false>, cpk::SpLay<cpk::SpDense>::kLds},
+             {(const void *)cpk::sp_small_kernel, cpk::kSpSmallLds},
+             {(const void *)cpk::rm_mw_kernel, cpk::kMwLds},
+             {(const void *)cpk::stream_mw_kernel, cpk::kMwLds},
+             {(const void *)cpk::ss_scan_kernel, cpk::kSsLds}};
+  for (const auto &k : lds)
+    if (hipFuncSetAttribute(k.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes) != hipSuccess) {
+      hipFree(c->tickets);
+      free(c);
+      return CPK_EDEVICE;
+    }
+  *out = c;
+  return CPK_OK;
+}
+
+void cpk_ctx_destroy(cpk_ctx ctx) {
+  if (!ctx) return;
+  DeviceGuard g(ctx->device);
+  if (ctx->trace) {
+    static const char *nm[8] = {"write staging in", "write enqueue", "write wait", "write staging out",
+                                "read staging in", "read enqueue", "read wait", "read staging out"};
+    for (int k = 0; k < 8; ++k)
+      if (ctx->tr_n[k])
+        fprintf(stderr, "cpk host trace: %-18s %8llu marks %12.1f us total\n", nm[k],
+                (unsigned long long)ctx->tr_n[k], ctx->tr_us[k]);
+  }
+  // (every DevBuf member: a new one is added here)
+  for (DevBuf *b : {&ctx->status, &ctx->sp_status, &ctx->sp_desc, &ctx->sp_units, &ctx->e4_bv, &ctx->ss_buf,
+                    &ctx->ms_buf, &ctx->ems_buf, &ctx->rm_buf, &ctx->fl_buf, &ctx->rm_copy})
+    if (b->p) hipFree(b->p);
+  if (ctx->tickets) hipFree(ctx->tickets);
+  if (ctx->probe_pin) hipHostFree(ctx->probe_pin);
+  pipe_destroy(ctx->pipe);
+  free(ctx);
+}
+
+int cpk_ctx_device(cpk_ctx ctx) { return ctx ? ctx->device : -1; }
+uint64_t cpk_ctx_small_fallbacks(cpk_ctx ctx) { return ctx ? ctx->small_fallbacks : 0; }
+int cpk_ctx_dense_windows(cpk_ctx ctx, void *stream, uint64_t *serial, uint64_t *given_back) {
+  if (!ctx || !serial || !given_back) return CPK_EINVAL;
+  if (!cpk::kDecCnt) return CPK_EUNSUPPORTED;  // (counted by the diagnostics build only)
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t c[2] = {0, 0};
+  if (hipMemcpyAsync(c, ctx->tickets + cpk::kTkDec + 1, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return CPK_EDEVICE;
+  *serial = c[0];
+  *given_back = c[1];
+  return CPK_OK;
+}
+
+// The device words at src[0..k) (k <= 8) on the host, after the work already
+// on stream s: one small kernel writes them to the context's pinned words.
+static int read_words(cpk_ctx ctx, hipStream_t s, std::initializer_list<const uint64_t *> src, uint64_t *dst) {
+  if (!ctx->probe_pin && hipHostMalloc((void **)&ctx->probe_pin, 8 * 8, hipHostMallocDefault) != hipSuccess) {
+    ctx->probe_pin = nullptr;
+    return CPK_ENOMEM;
+  }
+  cpk::Gather8 g = {};
+  uint32_t k = 0;
+  for (const uint64_t *p : src) g.p[k++] = p;
+  hipLaunchKernelGGL(cpk::gather8_kernel, dim3(1), dim3(64), 0, s, g, k, ctx->probe_pin);
+  if (hipStreamSynchronize(s) != hipSuccess) return CPK_EDEVICE;
+  for (uint32_t i = 0; i < k; ++i) dst[i] = ctx->probe_pin[i];
+  return CPK_OK;
+}
+
+// Single-pass encoder (encode_sp.hip): one launch, the look-back words
+// epoch-tagged (cleared only when the epoch wraps or the array grows).  Work
+// is ticketed per 8192-word chunk of a piece (a unit); a batch whose pieces
+// may be larger than one chunk (the hint) first gets its unit table (three
+// small kernels and the e4 scan, no host sync: the unit count stays on the
+// device).  sp_takes screens which batches it takes; cpk_encode_batch lets
+// the device choose by the piece sizes (e4_gate_kernel).
+static uint64_t sp_unit_bound(uint64_t n, uint64_t hint);
+// whether the single pass is enqueued at all (for the device to choose): a
+// size hint, and a unit table of bounded size for pieces over one chunk (a
+// loose hint would otherwise size it for nothing)
+static bool sp_takes(cpk_ctx ctx, uint32_t n, uint64_t max_seg_words) {
+  if (ctx->encoder == 0) return true;  // (CPK_ENCODER=0: single pass for every batch)
+  return ctx->encoder != 4 && max_seg_words != 0 && sp_unit_bound(n, max_seg_words) <= (1ull << 25);
+}
+
+// `units`: a bound on the batch's units when its pieces may exceed one
+// chunk (0: every piece is one unit)
+int sp_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, const uint64_t *pdesc,
+              const uint64_t *tin, uint32_t n, uint64_t hint, void *d_out, uint64_t *d_out_off,
+              hipStream_t s, bool gated = false, uint64_t units = 0, uint64_t out_cap = ~0ull) {
+  const uint64_t ucap = units ? units : n;  // look-back words (+ as many run-state words)
+  // (a grown array's words are undefined, and a look-back polls them:
+  // cleared below, as when the epoch wraps)
+  bool fresh = false;
+  if (int rc = reserve(ctx->sp_status, 2 * ucap, 8192, nullptr, &fresh)) return rc;
+  if (++ctx->sp_epoch > 0xffffu) {
+    ctx->sp_epoch = 1;
+    fresh = true;
+  }
+  if (fresh && hipMemsetAsync(ctx->sp_status.p, 0, ctx->sp_status.cap * 8, s) != hipSuccess) return CPK_EDEVICE;
+  uint64_t *ustate = ctx->sp_status.p + ucap;
+  const uint64_t *utab = nullptr, *nunits = nullptr;
+  if (units) {
+    // unit counts -> starts (e4 scan) -> unit table
+    const uint32_t nb = scan_blocks(n);
+    if (int rc = reserve(ctx->sp_units, (uint64_t)n + (n + 1) + nb + 1 + units)) return rc;
+    uint64_t *ucnt = ctx->sp_units.p, *ustart = ucnt + n, *bsum = ustart + (n + 1), *tab = bsum + nb + 1;
+    const unsigned tb = 256, tg = (n + tb - 1) / tb;
+    hipLaunchKernelGGL(cpk::sp_units_count_kernel, dim3(tg), dim3(tb), 0, s, d_swo, pdesc, n, hint, ucnt);
+    scan_launch(ucnt, n, bsum, ustart, s);
+    hipLaunchKernelGGL(cpk::sp_units_fill_kernel, dim3(tg), dim3(tb), 0, s, (const uint64_t *)ustart, n, tab);
+    utab = tab;
+    nunits = ustart + n;
+  }
+  // (gated: the ticket was set by e4_gate_kernel -- exhausted unless the
+  // batch is the single pass's)
+  if (!gated && hipMemsetAsync(ctx->tickets + cpk::kTkPlan, 0, 4, s) != hipSuccess) return CPK_EDEVICE;
+  // (gated: both forms enqueued, the one the gate did not pick returns at once)
+  const uint32_t *pick = gated ? ctx->tickets + cpk::kTkGate + 6 : nullptr;
+  constexpr uint32_t kLds = cpk::SpLay<cpk::SpDense>::kLds;
+  unsigned grid = (unsigned)(cpk::SpDense::kWpe * ctx->cus);
+  if (grid > ucap) grid = (unsigned)ucap;
+  if (pdesc)
+    hipLaunchKernelGGL(cpk::sp_encode_kernel<true>, dim3(grid), dim3(cpk::kSpThreads), kLds, s,
+                       (const uint64_t *)d_in, d_swo, pdesc, tin, n, (uint8_t *)d_out, d_out_off,
+                       ctx->sp_status.p, ctx->sp_epoch, ctx->tickets + cpk::kTkPlan, utab, nunits, ustate, hint,
+                       ctx->tickets + cpk::kTkErr, tin ? tin - 1 : (const uint64_t *)nullptr, pick, 0u, out_cap);
+  else
+    hipLaunchKernelGGL(cpk::sp_encode_kernel<false>, dim3(grid), dim3(cpk::kSpThreads), kLds, s,
+                       (const uint64_t *)d_in, d_swo, pdesc, tin, n, (uint8_t *)d_out, d_out_off,
+                       ctx->sp_status.p, ctx->sp_epoch, ctx->tickets + cpk::kTkPlan, utab, nunits, ustate, hint,
+                       ctx->tickets + cpk::kTkErr, tin ? tin - 1 : (const uint64_t *)nullptr, pick, 0u, out_cap);
+  if (gated && !pdesc) {
+    unsigned g2 = (unsigned)(cpk::SpSparse::kWpe * ctx->cus);
+    if (g2 > ucap) g2 = (unsigned)ucap;
+    hipLaunchKernelGGL((cpk::sp_encode_kernel<false, cpk::SpSparse>), dim3(g2), dim3(cpk::kSpThreads),
+                       cpk::SpLay<cpk::SpSparse>::kLds, s, (const uint64_t *)d_in, d_swo, pdesc, tin, n,
+                       (uint8_t *)d_out, d_out_off, ctx->sp_status.p, ctx->sp_epoch, ctx->tickets + cpk::kTkPlan, utab,
+                       nunits, ustate, hint, ctx->tickets + cpk::kTkErr, (const uint64_t *)nullptr, pick, 1u, out_cap);
+  }
+  return hip_ok(hipGetLastError());
+}
+
+// a bound on the units of n pieces of at most `hint` words (0: every piece
+// one unit); over 2^32 units: unsupported
+static uint64_t sp_unit_bound(uint64_t n, uint64_t hint) {
+  if (hint <= 64ull * cpk::kSpCS) return 0;
+  const uint64_t per = (hint + 64ull * cpk::kSpCS - 1) / (64ull * cpk::kSpCS);
+  return n * per;
+}
+
+// The size pass's rows for the emit pass (kE4RowBytes per 64-word step):
+// `stride` rows per piece from the hint when they fit in 4 GiB, else packed
+// by word offset (stride 0: the batch's word count is read back, synchronising
+// the stream)
+static int e4_rows(cpk_ctx ctx, const uint64_t *d_swo, uint32_t n, uint64_t hint, hipStream_t s,
+                   uint64_t &stride) {
+  stride = hint ? (hint + 63) / 64 : 0;
+  if (stride && stride > cpk::kE4MaxRows / (n ? n : 1)) stride = 0;  // (no overflow)
+  uint64_t rows;
+  if (stride) {
+    rows = (uint64_t)(n ? n : 1) * stride;
+  } else {
+    uint64_t ends[2];
+    int rc = read_words(ctx, s, {d_swo, d_swo + n}, ends);
+    if (rc) return rc;
+    rows = (ends[1] - ends[0]) / 64 + n + 1;
+  }
+  return reserve(ctx->e4_bv, rows, 0, [](uint64_t cap) { return cap * cpk::kE4RowBytes; });
+}
+
+// Encoder v4 (encode_v4.hip): size pass, scan, emit pass.  Pieces of any
+// size; a piece over the hint is reported (output undefined).  The size pass
+// leaves each 64-word step's run boundaries for the emit pass: `stride` rows
+// per piece from the hint, or packed by word offset when there is no hint (the
+// batch's word count is then read back, synchronising the stream).
+int e4_encode(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, uint64_t hint,
+              void *d_out, uint64_t *d_out_off, hipStream_t s, bool gate = false, uint64_t out_cap = ~0ull) {
+  int rc = reserve(ctx->status, (uint64_t)n + scan_blocks(n) + 1, 1024);
+  if (rc) return rc;
+  uint64_t stride;
+  rc = e4_rows(ctx, d_swo, n, hint, s, stride);
+  if (rc) return rc;
+  uint64_t *sizes = ctx->status.p, *bsum = ctx->status.p + n;
+  if (hipMemsetAsync(ctx->tickets, 0, cpk::kTkErr * 4, s) != hipSuccess) return CPK_EDEVICE;
+  if (gate) {
+    // which encoder takes the batch, decided on the device from the piece
+    // sizes (no host sync): the other's tickets are exhausted, so its
+    // kernels return at once (the scans then write offsets the single pass
+    // overwrites)
+    uint32_t *mm = ctx->tickets + cpk::kTkGate;
+    if (hipMemsetAsync(mm, 0xff, 4, s) != hipSuccess || hipMemsetAsync(mm + 1, 0, 4, s) != hipSuccess ||
+        hipMemsetAsync(mm + 3, 0, 4, s) != hipSuccess || hipMemsetAsync(mm + 7, 0, 4, s) != hipSuccess)
+      return CPK_EDEVICE;
+    const unsigned mg = n < 256u * 256u ? (unsigned)((n + 255) / 256) : 256u;
+    hipLaunchKernelGGL(cpk::e4_minmax_kernel, dim3(mg), dim3(256), 0, s, d_swo, n, mm, (const uint64_t *)d_in);
+    hipLaunchKernelGGL(cpk::e4_gate_kernel, dim3(1), dim3(64), 0, s, ctx->tickets, mg * 256u, (uint32_t)ctx->sp_form,
+                       d_swo, n);
+  }
+  const unsigned grid = e4_grid(ctx, n);
+  hipLaunchKernelGGL(cpk::e4_size_kernel, dim3(grid), dim3(cpk::kE4Threads), 0, s,
+                     (const uint64_t *)d_in, d_swo, n, sizes, ctx->tickets + cpk::kTkEnc, hint,
+                     ctx->tickets + cpk::kTkErr, ctx->e4_bv.p, stride,
+                     gate ? (const uint32_t *)(ctx->tickets + cpk::kTkGate + 2) : (const uint32_t *)nullptr,
+                     (const uint32_t *)nullptr);
+  scan_launch(sizes, n, bsum, d_out_off, s);
+  hipLaunchKernelGGL(cpk::e4_emit_kernel, dim3(grid), dim3(cpk::kE4Threads), cpk::kE4Lds, s,
+                     (const uint64_t *)d_in, d_swo, n, (const uint64_t *)d_out_off,
+                     (uint8_t *)d_out, ctx->tickets + cpk::kTkDec, (const uint64_t *)ctx->e4_bv.p,
+                     stride, gate ? (const uint32_t *)(ctx->tickets + cpk::kTkGate + 2) : (const uint32_t *)nullptr,
+                     (const uint64_t *)sizes, out_cap, ctx->tickets + cpk::kTkErr, (const uint32_t *)nullptr);
+  return hip_ok(hipGetLastError());
+}
+
+int cpk_encode_messages(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t nseg,
+                        const uint64_t *d_msg_seg_off, uint32_t nm, uint64_t max_seg_words,
+                        void *d_out, uint64_t *d_out_off, void *stream) {
+  return cpk_encode_messages_cap(ctx, d_in, d_swo, nseg, d_msg_seg_off, nm, max_seg_words, d_out, ~0ull,
+                                 d_out_off, stream);
+}
+int cpk_encode_messages_cap(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t nseg,
+                            const uint64_t *d_msg_seg_off, uint32_t nm, uint64_t max_seg_words,
+                            void *d_out, uint64_t out_cap, uint64_t *d_out_off, void *stream) {
+  if (!ctx || !d_out_off || (nm && !d_msg_seg_off) || (nseg && !d_swo)) return CPK_EINVAL;
+  if (((uintptr_t)d_out & 15) || ((uintptr_t)d_in & 7)) return CPK_EINVAL;
+  if (max_seg_words == 0) return CPK_EINVAL;  // (a bound is needed for the step rows)
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (nm == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
+  const uint64_t np = (uint64_t)nm + nseg;  // pieces: a table per message + the segments
+  if (np > 0xffffffffull) return CPK_EINVAL;
+  if (ctx->encoder == 0 || (ctx->encoder != 4 && np <= 1024)) {
+    // single pass (forced, or a small batch -- one SerializePacked.write:
+    // two launches instead of the two passes' nine; a large batch of mixed
+    // sizes takes the two passes, faster there): piece descriptors in
+    // message order + the tables' words
+    if (int rc = reserve(ctx->sp_desc, 2 * np + (uint64_t)nseg / 2 + nm + 2)) return rc;
+    // pdesc[2 np] | output bound | tables
+    uint64_t *pdesc = ctx->sp_desc.p, *tbuf = ctx->sp_desc.p + 2 * np + 1;
+    const unsigned tb = 256, tg = (nm + tb - 1) / tb;
+    hipLaunchKernelGGL(cpk::sp_msg_prep_kernel, dim3(tg), dim3(tb), 0, s, d_swo, d_msg_seg_off, nm, pdesc,
+                       tbuf, tbuf - 1);
+    // (tables are at most 257 words: the segments' hint bounds the units)
+    const uint64_t ub = sp_unit_bound(np, max_seg_words);
+    if (ub > 0xffffffffull) return CPK_EUNSUPPORTED;
+    return sp_launch(ctx, d_in, nullptr, pdesc, tbuf, (uint32_t)np, max_seg_words, d_out, d_out_off, s, false, ub,
+                     out_cap);
+  }
+  const uint32_t nb = scan_blocks(np);
+  // scratch: segment sizes | table sizes | message-order sizes | segment offsets | block sums |
+  // the segments largest first (u32) | their class counts (u32)
+  int rc = reserve(ctx->status, (uint64_t)nseg + nm + np + nseg + nb + 1 + nseg / 2 + 1 + cpk::kOrdClasses / 2, 1024);
+  if (rc) return rc;
+  uint64_t *ssize = ctx->status.p, *tsize = ssize + nseg, *comb = tsize + nm, *soff = comb + np;
+  uint64_t *bsum = soff + nseg;
+  uint32_t *sord = reinterpret_cast<uint32_t *>(bsum + nb + 1), *shist = sord + nseg + (nseg & 1);
+  uint64_t stride;
+  rc = e4_rows(ctx, d_swo, nseg, max_seg_words, s, stride);
+  if (rc) return rc;
+  if (hipMemsetAsync(ctx->tickets, 0, cpk::kTkErr * 4, s) != hipSuccess) return CPK_EDEVICE;
+  const unsigned tb = 256, tg = (nm + tb - 1) / tb;
+  const unsigned grid = e4_grid(ctx, nseg);
+  // (segments largest first, both passes: a wave takes a whole segment, and a
+  // 256 KiB one taken last kept the rest of the chip idle behind it)
+  const uint32_t *order = nullptr;
+  if (nseg && ctx->e4_order) {
+    ord_launch(nullptr, nseg, shist, sord, s, d_swo);
+    order = sord;
+  }
+  const uint32_t *size_order = ctx->e4_order == 1 ? order : nullptr;
+  if (nseg)
+    hipLaunchKernelGGL(cpk::e4_size_kernel, dim3(grid), dim3(cpk::kE4Threads), 0, s,
+                       (const uint64_t *)d_in, d_swo, nseg, ssize, ctx->tickets + cpk::kTkEnc,
+                       max_seg_words, ctx->tickets + cpk::kTkErr, ctx->e4_bv.p, stride, (const uint32_t *)nullptr,
+                       size_order);
+  hipLaunchKernelGGL(cpk::msg_table_size_kernel, dim3(tg), dim3(tb), 0, s, d_swo, d_msg_seg_off, nm,
+                     tsize);
+  hipLaunchKernelGGL(cpk::msg_interleave_kernel, dim3(tg), dim3(tb), 0, s, d_msg_seg_off, nm,
+                     (const uint64_t *)tsize, (const uint64_t *)ssize, comb);
+  scan_launch(comb, (uint32_t)np, bsum, d_out_off, s);
+  hipLaunchKernelGGL(cpk::msg_table_emit_kernel, dim3(tg), dim3(tb), 0, s, d_swo, d_msg_seg_off, nm,
+                     (const uint64_t *)d_out_off, soff, (uint8_t *)d_out, (const uint64_t *)tsize, out_cap,
+                     ctx->tickets + cpk::kTkErr);
+  if (nseg)
+    hipLaunchKernelGGL(cpk::e4_emit_kernel, dim3(grid), dim3(cpk::kE4Threads), cpk::kE4Lds, s,
+                       (const uint64_t *)d_in, d_swo, nseg, (const uint64_t *)soff, (uint8_t *)d_out,
+                       ctx->tickets + cpk::kTkDec, (const uint64_t *)ctx->e4_bv.p, stride, (const uint32_t *)nullptr,
+                       (const uint64_t *)ssize, out_cap, ctx->tickets + cpk::kTkErr, order);
+  return hip_ok(hipGetLastError());
+}
+
+int cpk_encode_batch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n,
+                     uint64_t max_seg_words, void *d_out, uint64_t *d_out_off, void *stream) {
+  return cpk_encode_batch_cap(ctx, d_in, d_swo, n, max_seg_words, d_out, ~0ull, d_out_off, stream);
+}
+int cpk_encode_batch_cap(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n,
+                         uint64_t max_seg_words, void *d_out, uint64_t out_cap, uint64_t *d_out_off,
+                         void *stream) {
+  if (!ctx || (!d_swo && n) || !d_out_off) return CPK_EINVAL;
+  if (((uintptr_t)d_out & 15) || ((uintptr_t)d_in & 7)) return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
+  if (!sp_takes(ctx, n, max_seg_words))
+    return e4_encode(ctx, d_in, d_swo, n, max_seg_words, d_out, d_out_off, s, false, out_cap);
+  if (ctx->encoder == 0) {
+    // (forced single pass: pieces of any size, several units for a large one)
+    uint64_t hint = max_seg_words;
+    if (!hint) {  // (no bound given: the batch's words bound every piece)
+      uint64_t ends[2];
+      int rc = read_words(ctx, s, {d_swo, d_swo + n}, ends);
+      if (rc) return rc;
+      hint = ends[1] - ends[0];
+    }
+    uint64_t ub = sp_unit_bound(n, hint);
+    if (hint > 64ull * cpk::kSpCS && !max_seg_words) ub = n + hint / (64ull * cpk::kSpCS) + 1;
+    if (ub > 0xffffffffull) return CPK_EUNSUPPORTED;
+    return sp_launch(ctx, d_in, d_swo, nullptr, nullptr, n, max_seg_words, d_out, d_out_off, s, false, ub,
+                     out_cap);
+  }
+  // by piece size: both enqueued, the device picks one (e4_gate_kernel);
+  // pieces over one chunk go to the single pass as several units
+  int rc = e4_encode(ctx, d_in, d_swo, n, max_seg_words, d_out, d_out_off, s, true, out_cap);
+  if (rc) return rc;
+  return sp_launch(ctx, d_in, d_swo, nullptr, nullptr, n, max_seg_words, d_out, d_out_off, s, true,
+                   sp_unit_bound(n, max_seg_words), out_cap);
+}
+
+int cpk_ctx_take_error(cpk_ctx ctx, void *stream) {
+  if (!ctx) return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t e = 0;
+  if (hipMemcpyAsync(&e, ctx->tickets + cpk::kTkErr, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return CPK_EDEVICE;
+  if (e && hipMemsetAsync(ctx->tickets + cpk::kTkErr, 0, 4, s) != hipSuccess) return CPK_EDEVICE;
+  // kErrHint: a piece over its size hint; kErrWait: a cross-workgroup wait
+  // timed out (cannot happen by design: every wave it waits on is resident);
+  // kErrCap: packed bytes would have passed the caller's output capacity
+  // (nothing was written there: ArrayOutputStream.java:40-42 -> IOException)
+  if (!e) return CPK_OK;
+  return (e & cpk::kErrWait) ? CPK_EDEVICE : (e & cpk::kErrCap) ? CPK_ENOMEM : CPK_EINVAL;
+}
+
+// one launch of the configured decoder (grid: as many workgroups per CU as
+// its LDS allows, at most 8; never more than the work needs)
+namespace {
+// which decoder a single-decoder call uses (the record-index one only when
+// forced: the by-density choice is made for batches, cpk_decode_batch)
+bool dec_v2(cpk_ctx ctx) { return ctx->decoder == 2; }
+
+void dec_launch(cpk_ctx ctx, bool stream, unsigned want, const uint8_t *packed, uint64_t *in_off,
+                const uint64_t *swo, uint32_t n, uint64_t *out, int32_t *status, uint64_t avail,
+                cpk::DecStreams sd, hipStream_t s, int which = 0) {
+  // which: 0 the context's choice, 1 the block map, 2 the record index, 3
+  // the block map's dense form (decode_kernel<.., true>)
+  const bool v2 = which ? which == 2 : dec_v2(ctx);
+  const bool dense = which == 3;
+  const uint32_t lds = v2 ? cpk::kD2Lds : cpk::kDecLds;
+  const unsigned per_cu = (unsigned)min(8u, 160u * 1024u / lds);
+  unsigned grid = per_cu * (unsigned)ctx->cus;
+  if (grid > want) grid = want;
+  if (grid == 0) grid = 1;
+  uint32_t *tk = ctx->tickets + cpk::kTkDec;
+  // (both decoders' kernels, every form, take the same arguments)
+  const auto kernel = v2      ? (stream ? cpk::decode2_kernel<true> : cpk::decode2_kernel<false>)
+                      : dense ? (stream ? cpk::decode_kernel<true, true> : cpk::decode_kernel<false, true>)
+                              : (stream ? cpk::decode_kernel<true> : cpk::decode_kernel<false>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(v2 ? cpk::kD2Threads : cpk::kDecThreads), lds, s, packed, in_off, swo, n,
+                     out, status, tk, avail, sd);
+}
+}  // namespace
+
+// probe: a batch of <= 32 pieces may read its extent back (one sync) to
+// decode a few large pieces as one stream.  The host forms pass false: they
+// know the sizes and take that path themselves (cpk_decode_host), so their
+// two-slot pipeline never blocks on it; nor does a stream being captured.
+
+int cpk_decode_batch(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off,
+                     const uint64_t *d_swo, uint32_t n, void *d_out, int32_t *d_status,
+                     void *stream) {
+  bool probe = n <= 32;
+  if (probe && ctx) {
+    DeviceGuard g(ctx->device);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+      probe = false;
+  }
+  return decode_batch_impl(ctx, d_packed, d_in_off, d_swo, n, d_out, d_status, stream, probe);
+}
+
+static int decode_batch_impl(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off, const uint64_t *d_swo,
+                             uint32_t n, void *d_out, int32_t *d_status, void *stream, bool probe) {
+  if (!ctx || (n && (!d_in_off || !d_swo || !d_status))) return CPK_EINVAL;
+  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 7)) return CPK_EINVAL;
+  if (n == 0) return CPK_OK;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (dec_tickets_reset(ctx, s) != hipSuccess)
+    return CPK_EDEVICE;
+  // persistent: blocks of 4 independent waves, as many per CU as the LDS holds
+  uint64_t *in_off = const_cast<uint64_t *>(d_in_off);
+  if (ctx->decoder != 3) {
+    dec_launch(ctx, false, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out,
+               d_status, 0, cpk::DecStreams{nullptr, nullptr, nullptr, 0, nullptr, nullptr}, s);
+    return hip_ok(hipGetLastError());
+  }
+  // by density, decided on the device (dec_gate_kernel): both enqueued, the
+  // one not chosen returns at its first instruction
+  uint32_t *skip = ctx->tickets + cpk::kTkGate + 8;  // [3]: block map, record index, dense block map
+  hipLaunchKernelGGL(cpk::dec_gate_kernel, dim3(1), dim3(64), 0, s, (const uint64_t *)d_in_off, d_swo, n, skip);
+  if (probe && n <= 32) {
+    // A few pieces: read their extent back (one sync).  With >= 8 MiB of
+    // words each on average the batch decoders would give a piece one wave
+    // (one 64 MiB piece: ~100 ms), so decode them as one stream, 256-byte
+    // blocks in parallel, and let the batch decoders skip when every piece
+    // ended exactly at its packed range's end (dec_stream_check_kernel);
+    // otherwise they run after it and report the batch form's statuses.
+    // (through pinned memory: four copies into pageable memory cost ~75 us
+    // per call, ADVICE r5, profiles/r6b_small_decode_launch_overhead.txt)
+    uint64_t e[4];
+    int rc0 = read_words(ctx, s, {d_in_off, d_in_off + n, d_swo, d_swo + n}, e);
+    if (rc0) return rc0;
+    if (e[3] - e[2] >= ((uint64_t)n << 20) && (e[0] & 15) == 0 && e[1] >= e[0]) {
+      if (int rc = reserve_fixed(ctx->fl_buf, 33 * 8)) return rc;
+      int rc = cpk_decode_stream(ctx, (const uint8_t *)d_packed + e[0], e[1] - e[0], d_swo, n, d_out, ctx->fl_buf.p,
+                                 d_status, s);
+      if (rc) return rc;
+      hipLaunchKernelGGL(cpk::dec_stream_check_kernel, dim3(1), dim3(64), 0, s, (const uint64_t *)ctx->fl_buf.p,
+                         (const uint64_t *)d_in_off, (const int32_t *)d_status, n, skip);
+      if (dec_tickets_reset(ctx, s) != hipSuccess)
+        return CPK_EDEVICE;
+    }
+  }
+  dec_launch(ctx, false, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out, d_status, 0,
+             cpk::DecStreams{nullptr, nullptr, nullptr, 0, nullptr, skip}, s, 1);
+  dec_launch(ctx, false, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out, d_status, 0,
+             cpk::DecStreams{nullptr, nullptr, nullptr, 0, nullptr, skip + 1}, s, 2);
+  dec_launch(ctx, false, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out, d_status, 0,
+             cpk::DecStreams{nullptr, nullptr, nullptr, 0, nullptr, skip + 2}, s, 3);
+  return hip_ok(hipGetLastError());
+}
+
+namespace {
+// streams of at least this many bytes (after the bound below) are cut into
+// blocks and decoded in parallel (stream_split.hip); shorter ones by one
+// workgroup (decode_mw.hip; one wave under kRmMwMin).  Device-resident
+// (tools/stream_bench.py, config-2 data, one piece): 0.32 MiB packed 0.17 ms
+// by the workgroup against 0.23 ms by the block path, 0.65 MiB 0.31 / 0.23
+constexpr uint64_t kSsMin = 384 * 1024;
+constexpr uint64_t kRmSsMin = 64 * 1024;  // cpk_read_message
+// cpk_read_message_host: streams under kRmMwMax bytes in one launch (pinned
+// memory, no DMA), by one wave (rm_small_kernel) under kRmMwMin, else by a
+// whole workgroup (rm_mw_kernel).  Measured (threshold_probe, config-2-like
+// messages): one wave 36.7 / mw 42.9 us at 3.9 KB packed, 51.2 / 45.7 at
+// 7.8 KB; mw 54 us at 64 KiB of words (one wave 151), 116 at 256 KiB (the
+// parallel block path 206)
+constexpr uint64_t kRmMwMin = 6 * 1024;
+constexpr uint64_t kRmMwMax = 512 * 1024;
+// From host memory the workgroup reads the packed bytes straight from pinned
+// memory (PCIe round trips per window) and the block path stages them by
+// DMA: the block path is ahead from 128 KiB there (passByBytes replay, 512
+// KiB messages: 806 us per iteration against 940 at 256 KiB and 1,190 at
+// 512 KiB, profiles/r6c_pass_by_bytes_mw*.txt)
+constexpr uint64_t kRmMwMaxHost = 128 * 1024;
+// the host path's packed bytes on the device: the largest one-launch stream and its read slack
+constexpr uint64_t kRmCopyBytes = kRmMwMax + 128;
+int rm_copy_reserve(cpk_ctx ctx) { return reserve_fixed(ctx->rm_copy, kRmCopyBytes); }
+uint64_t rm_mw_max(cpk_ctx ctx, bool host) {
+  const uint64_t d = host ? kRmMwMaxHost : kRmMwMax;
+  return ctx->rm_mw_max && ctx->rm_mw_max < kRmMwMax ? ctx->rm_mw_max : d;
+}
+
+// the bytes a stream of `words` words may take: 10 per word at most
+uint64_t ss_reach(uint64_t avail, uint64_t words) {
+  const uint64_t b = words > (~0ull - 16) / 10 ? ~0ull : 10 * words + 16;
+  return avail < b ? avail : b;
+}
+
+// the block map's scratch for nb blocks, in the context (grown on demand)
+int ss_bufs(cpk_ctx ctx, uint64_t nb, cpk::SsBufs &B) {
+  using namespace cpk;
+  const uint64_t ng = (nb + kSsGroup - 1) / kSsGroup;
+  // scratch layout (u64 entries)
+  const uint64_t need = 5 * nb + 3 * kSsCand * nb + (nb + 1) / 2 + 3 * kSsVar * ng + (kSsVar + 1) * nb +
+                        ((kSsVar + 1) * nb + 1) / 2 + (ng + 1) / 2 + ng + 4 * (nb + 1) + (nb + 1) / 2 + 2 + 2;
+  if (int rc = reserve(ctx->ss_buf, need)) return rc;
+  uint64_t *q = ctx->ss_buf.p;
+  auto take = [&](uint64_t k) {
+    uint64_t *r = q;
+    q += k;
+    return r;
+  };
+  B.X = take(nb);
+  B.W = take(nb);
+  B.C1 = take(nb);
+  B.L1 = take(nb);
+  B.WL1 = take(nb);
+  B.C2 = take(kSsCand * nb);
+  B.L2 = take(kSsCand * nb);
+  B.WL2 = take(kSsCand * nb);
+  B.N2 = (uint32_t *)take((nb + 1) / 2);
+  B.GE = take(kSsVar * ng);
+  B.GX = take(kSsVar * ng);
+  B.GW = take(kSsVar * ng);
+  B.VE = take((kSsVar + 1) * nb);
+  B.VW = (uint32_t *)take(((kSsVar + 1) * nb + 1) / 2);
+  B.GC = (uint32_t *)take((ng + 1) / 2);
+  B.GB = take(ng);
+  B.E = take(nb + 1);
+  B.WO = take(nb + 1);
+  B.sin = take(nb + 1);
+  B.sswo = take(nb + 1);
+  B.sst = (int32_t *)take((nb + 1) / 2);
+  B.flag = (uint32_t *)take(2);
+  B.lim = take(2);
+  return CPK_OK;
+}
+
+// parallel stream decode over at most `reach` bytes; enqueues the one-wave
+// decoder after it, which runs only if the parallel path met anything
+// irregular (it then decodes the whole stream, errors included)
+int ss_decode(cpk_ctx ctx, const uint8_t *pk, uint64_t avail, uint64_t reach, const uint64_t *swo, uint32_t n,
+              uint64_t *out, uint64_t *in_off, int32_t *status, hipStream_t s) {
+  using namespace cpk;
+  const uint64_t nb = (reach + kSsBlock - 1) / kSsBlock;
+  SsBufs B;
+  if (int rc = ss_bufs(ctx, nb, B)) return rc;
+  if (int rc = ss_map_launch(ctx, pk, reach, swo, n, nb, B, s)) return rc;
+  const unsigned tb = 256;
+  const uint64_t nsub = (nb + kSsSub - 1) / kSsSub;
+  hipLaunchKernelGGL(ss_bound_kernel, dim3((n + 1 + 63) / 64), dim3(64), 0, s, pk, swo, n, nb, in_off, B);
+  hipLaunchKernelGGL(ss_sub_kernel, dim3((unsigned)((nsub + 1 + tb - 1) / tb)), dim3(tb), 0, s, swo, n, nb,
+                     (const uint64_t *)in_off, B);
+  dec_launch(ctx, false, (unsigned)((nsub + 3) / 4), pk, B.sin, B.sswo, (uint32_t)nsub, out, B.sst, 0,
+             DecStreams{nullptr, nullptr, nullptr, 0, nullptr}, s);
+  hipLaunchKernelGGL(ss_check_kernel, dim3((unsigned)((nsub + tb - 1) / tb)), dim3(tb), 0, s, nsub, B);
+  hipLaunchKernelGGL(ss_final_kernel, dim3((n + tb - 1) / tb), dim3(tb), 0, s, n, status, ctx->tickets + kTkDec, B,
+                     getenv("CPK_STREAM_NO_FALLBACK") ? 1 : 0);
+  // the one-wave decoder: no ticket unless the parallel path gave up
+  dec_launch(ctx, true, 1, pk, in_off, swo, n, out, status, avail,
+             DecStreams{nullptr, nullptr, nullptr, 1, in_off + n}, s);
+  return hip_ok(hipGetLastError());
+}
+}  // namespace
+
+int cpk_decode_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
+                      const uint64_t *d_swo, uint32_t n, void *d_out, uint64_t *d_in_off,
+                      int32_t *d_status, void *stream) {
+  if (!ctx || (n && (!d_in_off || !d_swo || !d_status))) return CPK_EINVAL;
+  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 7)) return CPK_EINVAL;
+  if (n == 0) return CPK_OK;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (avail >= kSsMin && !getenv("CPK_STREAM_ONE_WAVE")) {
+    // the stream's word count bounds the bytes worth cutting into blocks
+    // (the rest of `avail` may be later messages): read it back
+    uint64_t ends[2];
+    int rc = read_words(ctx, s, {d_swo, d_swo + n}, ends);
+    if (rc) return rc;
+    const uint64_t reach = ss_reach(avail, ends[1] - ends[0]);
+    if (reach >= kSsMin)
+      return ss_decode(ctx, (const uint8_t *)d_packed, avail, reach, d_swo, n, (uint64_t *)d_out, d_in_off,
+                       d_status, s);
+  }
+  if (avail >= kRmMwMin && !getenv("CPK_STREAM_ONE_WAVE")) {
+    // a mid-size stream: one workgroup, its 16 waves sharing each piece's windows
+    hipLaunchKernelGGL(cpk::stream_mw_kernel, dim3(1), dim3(cpk::kMwThreads), cpk::kMwLds, s,
+                       (const uint8_t *)d_packed, avail, d_swo, n, (uint64_t *)d_out, d_in_off, d_status);
+    return hip_ok(hipGetLastError());
+  }
+  if (dec_tickets_reset(ctx, s) != hipSuccess)
+    return CPK_EDEVICE;
+  // one stream: one wave works, the others find no ticket
+  dec_launch(ctx, true, 1, (const uint8_t *)d_packed, d_in_off, d_swo, n, (uint64_t *)d_out, d_status, avail,
+             cpk::DecStreams{nullptr, nullptr, nullptr, 1, d_in_off + n}, s);
+  return hip_ok(hipGetLastError());
+}
+
+
+// A whole stream of packed messages (stream_split.hip, ms_*): the block map
+// over every byte, the blocks decoded into d_out, the frame chain, every
+// piece boundary checked, the result row read back (the one sync; a second
+// only when the chain made more entries than the context had room for).
+int cpk_decode_message_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail, uint64_t traversal_limit_words,
+                              void *d_out, uint64_t out_cap_words, uint64_t *d_msg_off, uint64_t *d_msg_seg_off,
+                              uint32_t msg_cap, uint64_t *d_seg_begin, uint64_t *d_seg_words, uint32_t seg_cap,
+                              uint64_t *h_info, void *stream) {
+  using namespace cpk;
+  if (!ctx || !h_info || (avail && !d_packed) || (out_cap_words && !d_out)) return CPK_EINVAL;
+  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_msg_off & 7) ||
+      ((uintptr_t)d_msg_seg_off & 7) || ((uintptr_t)d_seg_begin & 7) || ((uintptr_t)d_seg_words & 7))
+    return CPK_EINVAL;
+  if (seg_cap && (!d_seg_begin || !d_seg_words)) return CPK_EINVAL;
+  if (msg_cap && (!d_msg_off || !d_msg_seg_off)) return CPK_EINVAL;
+  for (int i = 0; i < CPK_MS_INFO_WORDS; ++i) h_info[i] = 0;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (avail == 0) {
+    if ((d_msg_off && hipMemsetAsync(d_msg_off, 0, 8, s) != hipSuccess) ||
+        (d_msg_seg_off && hipMemsetAsync(d_msg_seg_off, 0, 8, s) != hipSuccess))
+      return CPK_EDEVICE;
+    return CPK_OK;
+  }
+  // (entries the arrays hold: msg_cap + 1 and seg_cap; none without an array)
+  const int64_t msg_lim = d_msg_off && d_msg_seg_off ? (int64_t)msg_cap : -1;
+  const int64_t seg_lim = d_seg_begin && d_seg_words ? (int64_t)seg_cap : 0;
+  const uint64_t nb = (avail + kSsBlock - 1) / kSsBlock;
+  SsBufs B;
+  if (int rc = ss_bufs(ctx, nb, B)) return rc;
+  // the chain's entries: a message per 64 packed bytes to begin with
+  auto ms_bufs = [&](uint64_t entries, MsBufs &M) -> int {
+    // ctl [8] | result row [8] | X, S, P [cap each] | statuses [cap x i32]
+    if (int rc = reserve(ctx->ms_buf, entries, 0, [](uint64_t cap) { return (16 + 3 * cap + (cap + 1) / 2) * 8; }))
+      return rc;
+    M.mcap = ctx->ms_buf.cap;
+    M.ctl = ctx->ms_buf.p;
+    M.res = M.ctl + 8;
+    M.X = M.res + 8;
+    M.S = M.X + M.mcap;
+    M.P = M.S + M.mcap;
+    M.ST = (int32_t *)(M.P + M.mcap);
+    return CPK_OK;
+  };
+  MsBufs M;
+  if (int rc = ms_bufs(avail / 64 + 1024, M)) return rc;
+  const uint8_t *pk = (const uint8_t *)d_packed;
+  const uint64_t *out = (const uint64_t *)d_out;
+  if (int rc = ss_map_launch(ctx, pk, avail, nullptr, 0, nb, B, s)) return rc;
+  const unsigned tb = 256;
+  const uint64_t nsub = (nb + kSsSub - 1) / kSsSub;
+  hipLaunchKernelGGL(ms_end_kernel, dim3(1), dim3(64), 0, s, pk, nb, out_cap_words, B, M);
+  hipLaunchKernelGGL(ms_sub_kernel, dim3((unsigned)((nsub + 1 + tb - 1) / tb)), dim3(tb), 0, s, nb, B, M);
+  dec_launch(ctx, false, (unsigned)((nsub + 3) / 4), pk, B.sin, B.sswo, (uint32_t)nsub, (uint64_t *)d_out, B.sst, 0,
+             DecStreams{nullptr, nullptr, nullptr, 0, nullptr}, s);
+  hipLaunchKernelGGL(ss_check_kernel, dim3((unsigned)((nsub + tb - 1) / tb)), dim3(tb), 0, s, nsub, B);
+  uint64_t r[8];
+  for (int attempt = 0;; ++attempt) {
+    const unsigned waves = (unsigned)((M.mcap + 3) / 4), bgrid = waves < 8u * ctx->cus ? waves : 8u * ctx->cus;
+    hipLaunchKernelGGL(ms_chain_kernel, dim3(1), dim3(64), 0, s, out, nb, B, M, traversal_limit_words,
+                       d_msg_seg_off, msg_lim, d_seg_begin, d_seg_words, seg_lim);
+    hipLaunchKernelGGL(ms_bound_kernel, dim3(bgrid), dim3(256), 0, s, pk, out, nb, B, M, traversal_limit_words,
+                       d_msg_off, msg_lim);
+    hipLaunchKernelGGL(ms_final_kernel, dim3(1), dim3(64), 0, s, nb, B, M);
+    if (hipGetLastError() != hipSuccess) return CPK_EDEVICE;
+    if (int rc = read_words(ctx, s, {M.res, M.res + 1, M.res + 2, M.res + 3, M.res + 4, M.res + 5, M.res + 6,
+                                    M.res + 7}, r))
+      return rc;
+    if (!(r[6] & kMsShort) || attempt) break;
+    // more messages than entries: the chain and the checks again with room
+    // for all (the map and the words stay as they are)
+    if (int rc = ms_bufs(r[5], M)) return rc;
+    hipLaunchKernelGGL(ms_rearm_kernel, dim3(1), dim3(64), 0, s, M);
+  }
+  h_info[2] = r[7];
+  if (r[6] & kMsNoRoom) return CPK_ENOMEM;
+  if (r[6] & kMsShort) return CPK_EDEVICE;
+  if (r[6]) {
+    // the batch decoder rejected a block of the map (no such stream is known)
+    h_info[2] = 0;
+    h_info[4] = (uint64_t)(int64_t)CPK_EUNSUPPORTED;
+    return CPK_EUNSUPPORTED;
+  }
+  h_info[0] = r[0];
+  h_info[1] = r[1];
+  if ((int64_t)r[0] > msg_lim || (int64_t)r[1] > seg_lim) return CPK_ENOMEM;
+  h_info[2] = r[2];
+  h_info[3] = r[3];
+  h_info[4] = r[4];
+  return CPK_OK;
+}
+
+// A whole stream of unpacked messages packed (encode_ms.hip): the frame
+// chain over the words, its result row read back (the piece count sizes the
+// encoders' launches), the pieces through cpk_encode_batch_cap, then the
+// packed total and the context's error word read back.
+int cpk_encode_message_stream(cpk_ctx ctx, const void *d_in, uint64_t avail_words, uint64_t traversal_limit_words,
+                              void *d_out, uint64_t out_cap, uint64_t *d_out_off, uint32_t piece_cap,
+                              uint64_t *d_msg_piece, uint32_t msg_cap, uint64_t *h_info, void *stream) {
+  using namespace cpk;
+  if (!ctx || !h_info || (avail_words && !d_in) || (out_cap && !d_out)) return CPK_EINVAL;
+  if (((uintptr_t)d_in & 7) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_out_off & 7) || ((uintptr_t)d_msg_piece & 7))
+    return CPK_EINVAL;
+  if ((piece_cap && !d_out_off) || (msg_cap && !d_msg_piece)) return CPK_EINVAL;
+  for (int i = 0; i < CPK_EMS_INFO_WORDS; ++i) h_info[i] = 0;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (avail_words == 0) {
+    if ((d_out_off && hipMemsetAsync(d_out_off, 0, 8, s) != hipSuccess) ||
+        (d_msg_piece && hipMemsetAsync(d_msg_piece, 0, 8, s) != hipSuccess))
+      return CPK_EDEVICE;
+    return CPK_OK;
+  }
+  // (the last entry each array holds; none without an array.  A message of
+  // `count` segments is 1 + count pieces in at least 1 + count / 2 words:
+  // at most two pieces per word)
+  const int64_t msg_lim = d_msg_piece ? (int64_t)msg_cap : -1;
+  const uint64_t pmax = avail_words > 0x7fffffffull ? 0xffffffffull : 2 * avail_words;
+  const int64_t piece_lim = d_out_off ? (int64_t)(piece_cap < pmax ? piece_cap : pmax) : -1;
+  const uint64_t offs = (uint64_t)(piece_lim + 1);
+  if (int rc = reserve(ctx->ems_buf, offs, 1024, [](uint64_t cap) { return (kEmsRow + cap) * 8; })) return rc;
+  uint64_t *row = ctx->ems_buf.p, *poff = ctx->ems_buf.p + kEmsRow;
+  const uint64_t *errw = reinterpret_cast<const uint64_t *>(ctx->tickets + kTkErr);  // (the low half)
+  hipLaunchKernelGGL(ems_chain_kernel, dim3(1), dim3(64), 0, s, (const uint64_t *)d_in, avail_words,
+                     traversal_limit_words, poff, piece_lim, d_msg_piece, msg_lim, row);
+  if (hipGetLastError() != hipSuccess) return CPK_EDEVICE;
+  uint64_t r[6];
+  if (int rc = read_words(ctx, s, {row + kEmsMsgs, row + kEmsPieces, row + kEmsWords, row + kEmsTail,
+                                   row + kEmsMax, errw}, r))
+    return rc;
+  const uint32_t err0 = (uint32_t)r[5];  // (what earlier encodes left for cpk_ctx_take_error)
+  h_info[0] = r[0];
+  h_info[1] = r[1];
+  if ((int64_t)r[0] > msg_lim || (int64_t)r[1] > piece_lim) return CPK_ENOMEM;
+  h_info[2] = r[2];
+  h_info[4] = r[3];
+  h_info[5] = r[4];
+  const uint32_t n = (uint32_t)r[1];
+  if (n == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
+  // (every piece of a complete message is under 2^28 words and the tables
+  // are not empty: the largest piece is a bound the batch call takes)
+  if (int rc = cpk_encode_batch_cap(ctx, d_in, poff, n, r[4], d_out, out_cap, d_out_off, stream)) return rc;
+  // the packed total: the encoders write the last offset whatever the
+  // capacity (the scans; the single pass's look-back); the capacity verdict
+  // follows from it, and the error word tells a wait that timed out
+  uint64_t e[2];
+  if (int rc = read_words(ctx, s, {d_out_off + n, errw}, e)) return rc;
+  h_info[3] = e[0];
+  const uint32_t err1 = (uint32_t)e[1];
+  if ((err1 & ~err0) & (kErrWait | kErrHint)) return CPK_EDEVICE;
+  if (e[0] > out_cap) {
+    // (reported by the return value: the bit the encoders set for it is
+    // taken back unless an earlier call's is still waiting to be taken)
+    if (!(err0 & kErrCap) && hipMemsetD32Async((hipDeviceptr_t)(ctx->tickets + kTkErr), (int)(err1 & ~kErrCap), 1, s) !=
+                                 hipSuccess)
+      return CPK_EDEVICE;
+    return CPK_ENOMEM;
+  }
+  return CPK_OK;
+}
+}  // extern "C"
+static int read_message_impl(cpk_ctx ctx, const void *d_packed, uint64_t avail, uint64_t traversal_limit_words,
+                             void *d_out, uint64_t out_cap_words, uint64_t *d_info, void *stream,
+                             uint64_t *info_mirror, uint64_t seq = 0, bool *flagged = nullptr);
+extern "C" {
+int cpk_read_message(cpk_ctx ctx, const void *d_packed, uint64_t avail, uint64_t traversal_limit_words,
+                     void *d_out, uint64_t out_cap_words, uint64_t *d_info, void *stream) {
+  return read_message_impl(ctx, d_packed, avail, traversal_limit_words, d_out, out_cap_words, d_info, stream,
+                           nullptr);
+}
+}  // extern "C"
+
+// (info_mirror: where rm_final_kernel also copies the info row, e.g. pinned
+// host memory read after one sync; d_info null: a device row in rm_buf;
+// *flagged set: the one-launch kernel took it and writes seq to
+// info_mirror[kRmInfo] when done)
+static int read_message_impl(cpk_ctx ctx, const void *d_packed, uint64_t avail, uint64_t traversal_limit_words,
+                             void *d_out, uint64_t out_cap_words, uint64_t *d_info, void *stream,
+                             uint64_t *info_mirror, uint64_t seq, bool *flagged) {
+  if (flagged) *flagged = false;
+  using cpk::kRmPieces;
+  if (!ctx || (!d_info && !info_mirror) || (avail && !d_packed) || !d_out) return CPK_EINVAL;
+  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 7)) return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  // swo [515] | in_off [515] | statuses [514 x i32] | stream descriptor [4] | stream end [1] | pieces [1]
+  // | spare [2] | info row [517]
+  if (int rc = reserve_fixed(ctx->rm_buf, (2 * (kRmPieces + 1) + kRmPieces / 2 + 8 + cpk::kRmInfo) * 8ull)) return rc;
+  if (!d_info) d_info = ctx->rm_buf.p + 2 * (kRmPieces + 1) + kRmPieces / 2 + 8;
+  uint64_t *swo = ctx->rm_buf.p, *in_off = swo + kRmPieces + 1;
+  int32_t *pst = (int32_t *)(in_off + kRmPieces + 1);
+  uint64_t *sdesc = in_off + kRmPieces + 1 + kRmPieces / 2, *send_out = sdesc + 4, *npad = sdesc + 5;
+  // the pieces' sizes are on the device only: the stream decoder is sized by
+  // the bytes the caller's capacity can reach (10 per word at most)
+  const uint64_t reach = ss_reach(avail, out_cap_words + cpk::kRmHead);
+  // (a lower bar than cpk_decode_stream's: a message's one-wave decode is
+  //  ~0.5 GB/s, the parallel path ~250 us of fixed cost: even at 64 KiB)
+  const bool one = getenv("CPK_STREAM_ONE_WAVE") != nullptr;
+  if (!one && !dec_v2(ctx) && reach >= kRmMwMin && reach < rm_mw_max(ctx, info_mirror != nullptr)) {
+    // (the host path: pinned bytes, copied to the device in the kernel)
+    if (info_mirror && rm_copy_reserve(ctx)) return CPK_ENOMEM;
+    hipLaunchKernelGGL(cpk::rm_mw_kernel, dim3(1), dim3(cpk::kMwThreads), cpk::kMwLds, s,
+                       (const uint8_t *)d_packed, avail, traversal_limit_words, out_cap_words, swo, d_info, sdesc,
+                       (uint64_t *)d_out, in_off, pst, send_out, info_mirror,
+                       info_mirror ? (uint8_t *)ctx->rm_copy.p : nullptr, seq);
+    if (flagged) *flagged = info_mirror != nullptr;
+    return hip_ok(hipGetLastError());
+  }
+  const bool par = reach >= kRmSsMin && !one;
+  if (!par && !dec_v2(ctx)) {
+    // (the host path's packed bytes are pinned host memory: copied to the
+    // device once, in the kernel)
+    uint8_t *dcopy = nullptr;
+    if (info_mirror && reach + 96 <= kRmCopyBytes) {
+      if (rm_copy_reserve(ctx)) return CPK_ENOMEM;
+      dcopy = (uint8_t *)ctx->rm_copy.p;
+    }
+    hipLaunchKernelGGL(cpk::rm_small_kernel, dim3(1), dim3(cpk::kDecThreads), cpk::kDecLds, s,
+                       (const uint8_t *)d_packed, avail, traversal_limit_words, out_cap_words, swo, d_info, sdesc,
+                       ctx->tickets + cpk::kTkDec, (uint64_t *)d_out, in_off, pst, send_out, info_mirror, dcopy,
+                       seq);
+    if (flagged) *flagged = info_mirror != nullptr;
+    return hip_ok(hipGetLastError());
+  }
+  hipLaunchKernelGGL(cpk::rm_table_kernel, dim3(1), dim3(64), 0, s, (const uint8_t *)d_packed, avail,
+                     traversal_limit_words, out_cap_words, swo, d_info, sdesc,
+                     par ? (uint32_t *)nullptr : ctx->tickets + cpk::kTkDec);
+  int rc;
+  if (par) {
+    // every piece, the padding included, gets a status; the last carries the stream's
+    rc = ss_decode(ctx, (const uint8_t *)d_packed, avail, reach, swo, kRmPieces, (uint64_t *)d_out, in_off, pst, s);
+  } else {
+    // one wave over the table's pieces and the segments (the piece count is
+    // on the device: a one-stream descriptor), none of the padding; its
+    // tickets were zeroed by rm_table_kernel
+    dec_launch(ctx, true, 1, (const uint8_t *)d_packed, in_off, swo, kRmPieces, (uint64_t *)d_out, pst, avail,
+               cpk::DecStreams{sdesc, sdesc + 1, sdesc + 2, 1, send_out}, s);
+    rc = hip_ok(hipGetLastError());
+  }
+  if (rc) return rc;
+  hipLaunchKernelGGL(cpk::rm_final_kernel, dim3(1), dim3(64), 0, s, par ? (const uint64_t *)(in_off + kRmPieces)
+                                                                        : (const uint64_t *)send_out,
+                     (const int32_t *)pst, par ? (const uint64_t *)npad : (const uint64_t *)(sdesc + 3), d_info,
+                     info_mirror);
+  return hip_ok(hipGetLastError());
+}
+extern "C" {
+
+int cpk_decode_messages(cpk_ctx ctx, const void *d_packed, const uint64_t *d_msg_off, uint32_t nm,
+                        uint64_t traversal_limit_words, void *d_out, uint64_t out_cap_words,
+                        uint64_t *d_seg_word_off, uint64_t *d_seg_in_off, int32_t *d_seg_status,
+                        uint32_t seg_cap, uint64_t *d_msg_seg_off, int32_t *d_msg_status,
+                        uint64_t *h_totals, void *stream) {
+  if (!ctx || !h_totals || (nm && (!d_msg_off || !d_msg_seg_off || !d_msg_status))) return CPK_EINVAL;
+  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 7)) return CPK_EINVAL;
+  h_totals[0] = h_totals[1] = 0;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (nm == 0) return hip_ok(hipMemsetAsync(d_msg_seg_off, 0, 8, s));
+  // scratch: words | begin | words offsets [nm+1] | block sums x2
+  const uint32_t nb = scan_blocks(nm);
+  // (+ the stream order: nm u32 and kOrdClasses u32)
+  int rc = reserve(ctx->status, 3ull * nm + 1 + 2ull * nb + (nm + 1) / 2 + cpk::kOrdClasses / 2, 1024);
+  if (rc) return rc;
+  uint64_t *mwords = ctx->status.p, *mbeg = mwords + nm, *mwoff = mbeg + nm;
+  uint64_t *bs0 = mwoff + nm + 1, *bs1 = bs0 + nb;
+  uint32_t *ord = reinterpret_cast<uint32_t *>(bs1 + nb), *ohist = ord + ((nm + 1) & ~1u);
+  const unsigned tb = 256, tg = (nm + tb - 1) / tb;
+  // the segment counts go to d_msg_seg_off[0..nm) and are scanned into it
+  // (e4_scan_down: each thread reads its entries before it writes them)
+  hipLaunchKernelGGL(cpk::msg_table_kernel, dim3(tg), dim3(tb), 0, s, (const uint8_t *)d_packed,
+                     d_msg_off, nm, traversal_limit_words, mwords, d_msg_seg_off, mbeg, d_msg_status);
+  scan_launch(mwords, nm, bs0, mwoff, s);
+  scan_launch(d_msg_seg_off, nm, bs1, d_msg_seg_off, s);
+  uint64_t pk[2] = {0, 0};  // the messages' packed range (the decoder's density choice)
+  if (hipGetLastError() != hipSuccess) return CPK_EDEVICE;
+  {
+    uint64_t w[4];
+    const int rcw = read_words(ctx, s, {mwoff + nm, d_msg_seg_off + nm, d_msg_off, d_msg_off + nm}, w);
+    if (rcw) return rcw;
+    h_totals[0] = w[0];
+    h_totals[1] = w[1];
+    pk[0] = w[2];
+    pk[1] = w[3];
+  }
+  if (h_totals[0] > out_cap_words || h_totals[1] > seg_cap) return CPK_ENOMEM;
+  if (h_totals[1] && (!d_seg_word_off || !d_seg_in_off || !d_seg_status)) return CPK_EINVAL;
+  if (!d_seg_word_off) return CPK_OK;  // (no segments: every table failed)
+  hipLaunchKernelGGL(cpk::msg_swo_kernel, dim3(tg), dim3(tb), 0, s, (const uint8_t *)d_packed,
+                     d_msg_off, nm, traversal_limit_words, (const uint64_t *)mwoff,
+                     (const uint64_t *)d_msg_seg_off, (const int32_t *)d_msg_status, d_seg_word_off);
+  if (h_totals[1]) {
+    if (dec_tickets_reset(ctx, s) != hipSuccess)
+      return CPK_EDEVICE;
+    // the messages' streams largest first (ord_*: a counting sort by size class)
+    ord_launch(mwords, nm, ohist, ord, s);
+    // the stream ends overwrite the words array (no longer needed); dense
+    // batches (packed bytes >= 80 % of the words') take the block map's
+    // dense form, as dec_gate_kernel picks it for cpk_decode_batch (config 3:
+    // 48.0 -> 44.4 ms once the stream form's uniform values sat in scalar
+    // registers -- with 36 B/lane of spills it had been 49.9,
+    // profiles/r5aa_stream_sgpr.txt)
+    const bool dense = ctx->decoder == 3 && pk[1] >= pk[0] && 100 * (pk[1] - pk[0]) >= 80 * 8 * h_totals[0];
+    dec_launch(ctx, true, (nm + 3) / 4, (const uint8_t *)d_packed, d_seg_in_off, (const uint64_t *)d_seg_word_off,
+               (uint32_t)h_totals[1], (uint64_t *)d_out, d_seg_status, 0,
+               cpk::DecStreams{mbeg, d_msg_off + 1, d_msg_seg_off, nm, mwords, nullptr,
+                               ord},
+               s, dense ? 3 : 0);
+    hipLaunchKernelGGL(cpk::msg_final_kernel, dim3(tg), dim3(tb), 0, s, d_msg_off, nm,
+                       (const uint64_t *)d_msg_seg_off, (const uint64_t *)mwords,
+                       (const int32_t *)d_seg_status, d_msg_status);
+  }
+  return hip_ok(hipGetLastError());
+}
+
+int cpk_decode_stream_host(cpk_ctx ctx, const void *h_packed, uint64_t avail,
+                           const uint64_t *h_swo, uint32_t n, void *h_out, uint64_t *h_in_off,
+                           int32_t *h_status) {
+  if (!ctx || !h_swo || !h_in_off || !h_status) return CPK_EINVAL;
+  if (n == 0) {
+    h_in_off[0] = 0;
+    return CPK_OK;
+  }
+  for (uint32_t i = 0; i < n; ++i)
+    if (h_swo[i + 1] < h_swo[i]) return CPK_EINVAL;
+  const uint64_t words = h_swo[n] - h_swo[0];
+  if ((!h_packed && avail) || (!h_out && words)) return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  // only the bytes the stream can reach are staged (the rest of `avail` may
+  // be later messages), through the context's pinned slot 0 (grow-only: no
+  // allocation once it is large enough)
+  const uint64_t R = ss_reach(avail, words);
+  HostPipe *p = nullptr;
+  // meta: swo | in_off | status (int32)
+  int rc = pipe_get(ctx, R, words * 8, 2 * (n + 1ull) + n / 2 + 1, &p, 1);
+  if (rc) return rc;
+  HostSlot &sl = p->slot[0];
+  uint64_t *m = sl.pin_meta, *dm = sl.d_meta;
+  for (uint32_t i = 0; i <= n; ++i) m[i] = h_swo[i] - h_swo[0];
+  memset((uint8_t *)sl.pin_in + R, 0, 64);  // (the decoder's read slack)
+  if (hipMemcpyAsync(dm, m, (n + 1) * 8ull, hipMemcpyHostToDevice, p->sk) ||
+      h2d_pipelined(sl.d_in, sl.pin_in, h_packed, R, p->sk) ||
+      hipMemcpyAsync((uint8_t *)sl.d_in + R, (uint8_t *)sl.pin_in + R, 64, hipMemcpyHostToDevice, p->sk))
+    return CPK_EDEVICE;
+  rc = cpk_decode_stream(ctx, sl.d_in, R, dm, n, sl.d_out, dm + n + 1, (int32_t *)(dm + 2 * (n + 1ull)), p->sk);
+  if (rc) {
+    pipe_drain(p);
+    return rc;
+  }
+  if (hipMemcpyAsync(m + n + 1, dm + n + 1, (n + 1) * 8ull + n * 4ull, hipMemcpyDeviceToHost, p->sk))
+    return CPK_EDEVICE;
+  if (words) {
+    if (d2h_pipelined((uint8_t *)h_out + 8 * h_swo[0], sl.pin_out, sl.d_out, words * 8, p->sk, sl.eh, sl.ed))
+      return CPK_EDEVICE;
+  } else if (hipStreamSynchronize(p->sk)) {
+    return CPK_EDEVICE;
+  }
+  memcpy(h_in_off, m + n + 1, (n + 1) * 8ull);
+  memcpy(h_status, m + 2 * (n + 1ull), n * 4ull);
+  for (uint32_t i = 0; i < n; ++i)
+    if (h_status[i] != CPK_OK) return h_status[i];
+  return CPK_OK;
+}
+
+// The info row a read left, for the caller: its head (status, bytes consumed,
+// segment count, words needed) and, for a message read whole, the segment
+// offsets from the first segment's word.  -> the status; w0, words: the
+// segments only in the decoder's output (the table's words lead it)
+static int rm_info_out(const uint64_t *info, uint64_t *h_info, uint64_t &w0, uint64_t &words) {
+  const int st = (int)(int64_t)info[0];
+  const uint32_t count = (uint32_t)info[2];
+  for (int i = 0; i < 4; ++i) h_info[i] = info[i];
+  if (st != CPK_OK) return st;
+  w0 = info[4];
+  words = info[4 + count] - w0;
+  for (uint32_t i = 0; i <= count; ++i) h_info[4 + i] = info[4 + i] - w0;
+  return CPK_OK;
+}
+
+int cpk_read_message_host(cpk_ctx ctx, const void *h_packed, uint64_t avail, uint64_t traversal_limit_words,
+                          void *h_out, uint64_t out_cap_words, uint64_t *h_info) {
+  using cpk::kRmInfo;
+  if (!ctx || !h_info || (avail && !h_packed) || (out_cap_words && !h_out)) return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  // only the bytes the caller's capacity can reach are staged (the rest of
+  // `avail` may be later messages)
+  const uint64_t R = ss_reach(avail, out_cap_words + cpk::kRmHead);
+  HostPipe *p = nullptr;
+  int rc = pipe_get(ctx, R, (out_cap_words + cpk::kRmHead) * 8, kRmInfo + 1, &p, 1);
+  if (rc) return rc;
+  HostSlot &sl = p->slot[0];
+  uint64_t *info = sl.pin_meta;
+  TrClock tc(ctx);
+  if (R < rm_mw_max(ctx, true) && !getenv("CPK_NO_SMALL")) {
+    // the one-wave range: the kernels read the packed bytes from the pinned
+    // slot and write the words and the info row into pinned memory in place
+    // -- no DMA either way, one sync
+    memcpy(sl.pin_in, h_packed, R);
+    memset((uint8_t *)sl.pin_in + R, 0, 64);
+    tc.mark(kTrRIn);
+    const uint64_t seq = small_arm(ctx, info + kRmInfo);
+    bool flagged = false;
+    rc = read_message_impl(ctx, sl.pin_in, R, traversal_limit_words, sl.pin_out, out_cap_words, nullptr, p->sk,
+                           info, seq, &flagged);
+    if (rc) {
+      pipe_drain(p);
+      return rc;
+    }
+    tc.mark(kTrRLaunch);
+    if (flagged ? small_wait(ctx, p->sk, info + kRmInfo, seq) : hipStreamSynchronize(p->sk)) return CPK_EDEVICE;
+    tc.mark(kTrRWait);
+    uint64_t w0, words;
+    if (int st = rm_info_out(info, h_info, w0, words)) return st;
+    if (words) memcpy(h_out, (const uint64_t *)sl.pin_out + w0, words * 8);
+    tc.mark(kTrROut);
+    return CPK_OK;
+  }
+  // (the bytes chunk by chunk, DMA under the host copy; then the decoder's
+  // 64 bytes of read slack)
+  memset((uint8_t *)sl.pin_in + R, 0, 64);
+  if (h2d_pipelined(sl.d_in, sl.pin_in, h_packed, R, p->sk) ||
+      hipMemcpyAsync((uint8_t *)sl.d_in + R, (uint8_t *)sl.pin_in + R, 64, hipMemcpyHostToDevice, p->sk))
+    return CPK_EDEVICE;
+  tc.mark(kTrRIn);
+  rc = cpk_read_message(ctx, sl.d_in, R, traversal_limit_words, sl.d_out, out_cap_words, sl.d_meta, p->sk);
+  if (rc) {
+    pipe_drain(p);
+    return rc;
+  }
+  if (hipMemcpyAsync(info, sl.d_meta, kRmInfo * 8ull, hipMemcpyDeviceToHost, p->sk)) return CPK_EDEVICE;
+  tc.mark(kTrRLaunch);
+  if (hipStreamSynchronize(p->sk)) return CPK_EDEVICE;
+  tc.mark(kTrRWait);
+  uint64_t w0, words;
+  if (int st = rm_info_out(info, h_info, w0, words)) return st;
+  // (the words chunk by chunk: each chunk's copy-out under the next's DMA)
+  if (words && d2h_pipelined(h_out, sl.pin_out, (uint64_t *)sl.d_out + w0, words * 8, p->sk, sl.eh, sl.ed))
+    return CPK_EDEVICE;
+  tc.mark(kTrROut);
+  return CPK_OK;
+}
+
+int cpk_generate(cpk_ctx ctx, const cpk_gen_params *params, const uint64_t *d_swo, uint32_t n,
+                 void *d_out, void *stream) {
+  if (!ctx || !params) return CPK_EINVAL;
+  if (n == 0) return CPK_OK;
+  DeviceGuard g(ctx->device);
+  unsigned grid = (n + 255) / 256;
+  hipLaunchKernelGGL(cpk::generate_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *params,
+                     d_swo, n, (uint64_t *)d_out);
+  return hip_ok(hipGetLastError());
+}
+
+int cpk_count_mismatch(cpk_ctx ctx, const void *d_a, const void *d_b, uint64_t words,
+                       uint64_t *d_mismatch, void *stream) {
+  if (!ctx) return CPK_EINVAL;
+  if (words == 0) return CPK_OK;
+  DeviceGuard g(ctx->device);
+  unsigned grid = (unsigned)(8 * ctx->cus);
+  hipLaunchKernelGGL(cpk::mismatch_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                     (const uint64_t *)d_a, (const uint64_t *)d_b, words,
+                     (unsigned long long *)d_mismatch);
+  return hip_ok(hipGetLastError());
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // Host-memory forms of the batch codec (cpk_encode_host / cpk_decode_host):
 // the socket/file ByteBuffer path of SerializePacked.java:75-96, :119-134.
-// Included from packed_codec.hip.
+// Included from host_api.hip.
 //
 // The batch is cut into chunks of whole pieces (~CPK_HOST_CHUNK_MB of
 // unpacked words each) that flow through two staging slots, each a pinned
