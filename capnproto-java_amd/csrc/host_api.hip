@@ -1207,27 +1207,19 @@ int cpk_decode_stream_host(cpk_ctx ctx, const void *h_packed, uint64_t avail,
   // meta: swo | in_off | status (int32)
   int rc = pipe_get(ctx, R, words * 8, 2 * (n + 1ull) + n / 2 + 1, &p, 1);
   if (rc) return rc;
+  PipeGuard guard{p};
   HostSlot &sl = p->slot[0];
   uint64_t *m = sl.pin_meta, *dm = sl.d_meta;
   for (uint32_t i = 0; i <= n; ++i) m[i] = h_swo[i] - h_swo[0];
-  memset((uint8_t *)sl.pin_in + R, 0, 64);  // (the decoder's read slack)
   if (hipMemcpyAsync(dm, m, (n + 1) * 8ull, hipMemcpyHostToDevice, p->sk) ||
-      h2d_pipelined(sl.d_in, sl.pin_in, h_packed, R, p->sk) ||
-      hipMemcpyAsync((uint8_t *)sl.d_in + R, (uint8_t *)sl.pin_in + R, 64, hipMemcpyHostToDevice, p->sk))
+      stage_in(sl, h_packed, R, 64, p->sk))  // (64: the decoder's read slack)
     return CPK_EDEVICE;
   rc = cpk_decode_stream(ctx, sl.d_in, R, dm, n, sl.d_out, dm + n + 1, (int32_t *)(dm + 2 * (n + 1ull)), p->sk);
-  if (rc) {
-    pipe_drain(p);
-    return rc;
-  }
-  if (hipMemcpyAsync(m + n + 1, dm + n + 1, (n + 1) * 8ull + n * 4ull, hipMemcpyDeviceToHost, p->sk))
+  if (rc) return rc;
+  if (hipMemcpyAsync(m + n + 1, dm + n + 1, (n + 1) * 8ull + n * 4ull, hipMemcpyDeviceToHost, p->sk) ||
+      stage_out(sl, (uint8_t *)h_out + 8 * h_swo[0], sl.d_out, words * 8, p->sk))
     return CPK_EDEVICE;
-  if (words) {
-    if (d2h_pipelined((uint8_t *)h_out + 8 * h_swo[0], sl.pin_out, sl.d_out, words * 8, p->sk, sl.eh, sl.ed))
-      return CPK_EDEVICE;
-  } else if (hipStreamSynchronize(p->sk)) {
-    return CPK_EDEVICE;
-  }
+  guard.done();
   memcpy(h_in_off, m + n + 1, (n + 1) * 8ull);
   memcpy(h_status, m + 2 * (n + 1ull), n * 4ull);
   for (uint32_t i = 0; i < n; ++i)
@@ -1261,6 +1253,7 @@ int cpk_read_message_host(cpk_ctx ctx, const void *h_packed, uint64_t avail, uin
   HostPipe *p = nullptr;
   int rc = pipe_get(ctx, R, (out_cap_words + cpk::kRmHead) * 8, kRmInfo + 1, &p, 1);
   if (rc) return rc;
+  PipeGuard guard{p};
   HostSlot &sl = p->slot[0];
   uint64_t *info = sl.pin_meta;
   TrClock tc(ctx);
@@ -1275,12 +1268,10 @@ int cpk_read_message_host(cpk_ctx ctx, const void *h_packed, uint64_t avail, uin
     bool flagged = false;
     rc = read_message_impl(ctx, sl.pin_in, R, traversal_limit_words, sl.pin_out, out_cap_words, nullptr, p->sk,
                            info, seq, &flagged);
-    if (rc) {
-      pipe_drain(p);
-      return rc;
-    }
+    if (rc) return rc;
     tc.mark(kTrRLaunch);
     if (flagged ? small_wait(ctx, p->sk, info + kRmInfo, seq) : hipStreamSynchronize(p->sk)) return CPK_EDEVICE;
+    guard.done();
     tc.mark(kTrRWait);
     uint64_t w0, words;
     if (int st = rm_info_out(info, h_info, w0, words)) return st;
@@ -1290,25 +1281,20 @@ int cpk_read_message_host(cpk_ctx ctx, const void *h_packed, uint64_t avail, uin
   }
   // (the bytes chunk by chunk, DMA under the host copy; then the decoder's
   // 64 bytes of read slack)
-  memset((uint8_t *)sl.pin_in + R, 0, 64);
-  if (h2d_pipelined(sl.d_in, sl.pin_in, h_packed, R, p->sk) ||
-      hipMemcpyAsync((uint8_t *)sl.d_in + R, (uint8_t *)sl.pin_in + R, 64, hipMemcpyHostToDevice, p->sk))
-    return CPK_EDEVICE;
+  if (stage_in(sl, h_packed, R, 64, p->sk)) return CPK_EDEVICE;
   tc.mark(kTrRIn);
   rc = cpk_read_message(ctx, sl.d_in, R, traversal_limit_words, sl.d_out, out_cap_words, sl.d_meta, p->sk);
-  if (rc) {
-    pipe_drain(p);
-    return rc;
-  }
+  if (rc) return rc;
   if (hipMemcpyAsync(info, sl.d_meta, kRmInfo * 8ull, hipMemcpyDeviceToHost, p->sk)) return CPK_EDEVICE;
   tc.mark(kTrRLaunch);
   if (hipStreamSynchronize(p->sk)) return CPK_EDEVICE;
   tc.mark(kTrRWait);
   uint64_t w0, words;
-  if (int st = rm_info_out(info, h_info, w0, words)) return st;
+  const int st = rm_info_out(info, h_info, w0, words);
   // (the words chunk by chunk: each chunk's copy-out under the next's DMA)
-  if (words && d2h_pipelined(h_out, sl.pin_out, (uint64_t *)sl.d_out + w0, words * 8, p->sk, sl.eh, sl.ed))
-    return CPK_EDEVICE;
+  if (!st && words && stage_out(sl, h_out, (uint64_t *)sl.d_out + w0, words * 8, p->sk)) return CPK_EDEVICE;
+  guard.done();
+  if (st) return st;
   tc.mark(kTrROut);
   return CPK_OK;
 }

@@ -1,10 +1,10 @@
-// Host-memory forms of the batch codec (cpk_encode_host / cpk_decode_host):
-// the socket/file ByteBuffer path of SerializePacked.java:75-96, :119-134.
-// Included from host_api.hip.
+// Staging of the host-memory forms: the socket/file ByteBuffer path of
+// SerializePacked.java:75-96, :119-134.  Included from host_api.hip.
 //
-// The batch is cut into chunks of whole pieces (~CPK_HOST_CHUNK_MB of
-// unpacked words each) that flow through two staging slots, each a pinned
-// host buffer pair and a device buffer pair:
+// The chunk pipeline (run_chunks).  A batch is cut into chunks of whole
+// pieces or messages (~CPK_HOST_CHUNK_MB of unpacked words each) that flow
+// through two staging slots, each a pinned host buffer pair and a device
+// buffer pair:
 //
 //   host threads   copy-in(k) ............ copy-out(k-2)
 //   copy stream    H2D(k)
@@ -15,7 +15,18 @@
 // runs at 53 GiB/s each way (full duplex) and a threaded memcpy into pinned
 // memory at 80-100 GiB/s (tools/host_copy_probe.cpp), so the pipeline is
 // bounded by the DMA of the larger side.  Kernels of consecutive chunks run
-// in order on one stream (they share the context's workspace).
+// in order on one stream (they share the context's workspace).  Its forms
+// give it a chunk's meta words, device call and landing, nothing else:
+// cpk_encode_host[_gather], cpk_decode_host, cpk_encode_messages_host[_gather].
+//
+// The slot stager (stage_in / stage_out).  One transfer of unknown length
+// through slot 0, its host copies under its own DMA: cpk_decode_stream_host
+// and cpk_read_message_host (host_api.hip), cpk_decode_message_stream_host,
+// cpk_encode_message_stream_host, and each chunk of cpk_decode_messages_host
+// (synchronous per chunk: a table pass sizes the chunk's output first).
+//
+// Every form holds a PipeGuard from its first enqueue on: an error return
+// waits for what is still in flight on the pinned slots.
 
 struct HostSlot {
   void *pin_in = nullptr, *pin_out = nullptr, *d_in = nullptr, *d_out = nullptr;
@@ -97,7 +108,24 @@ void pipe_destroy(HostPipe *p) {
   delete p;
 }
 
-// the context's pipe with staging of at least the given sizes (grow-only)
+// wait for everything the pipe has in flight
+void pipe_drain(HostPipe *p) {
+  hipStreamSynchronize(p->sh);
+  hipStreamSynchronize(p->sk);
+  hipStreamSynchronize(p->sd);
+}
+
+// Held by a host form from its first enqueue: leaving with an error drains
+// the pipe, so that no copy or kernel still runs on the pinned slots when the
+// caller's next call overwrites them.  done(): all of it has been waited for.
+struct PipeGuard {
+  HostPipe *p;
+  ~PipeGuard() {
+    if (p) pipe_drain(p);
+  }
+  void done() { p = nullptr; }
+};
+
 // One large transfer through a pinned slot, pipelined in chunks of
 // kPipeChunk: the threaded host copy of chunk k+1 overlaps the DMA of chunk k
 // (single-slot host forms: one message or stream of unknown length).
@@ -135,6 +163,22 @@ int d2h_pipelined(void *dst, void *pin, const void *dev, uint64_t bytes, hipStre
   return CPK_OK;
 }
 
+// The slot stager.  In: `bytes` of src through pin_in to d_in on s, then
+// `slack` zero bytes behind them (the decoders read whole lines past the end).
+int stage_in(HostSlot &sl, const void *src, uint64_t bytes, uint32_t slack, hipStream_t s) {
+  uint8_t *pin = (uint8_t *)sl.pin_in + bytes;
+  memset(pin, 0, slack);
+  if (h2d_pipelined(sl.d_in, sl.pin_in, src, bytes, s)) return CPK_EDEVICE;
+  return slack ? hip_ok(hipMemcpyAsync((uint8_t *)sl.d_in + bytes, pin, slack, hipMemcpyHostToDevice, s)) : CPK_OK;
+}
+// Out: `bytes` at dev (in d_out) through pin_out to dst on s, which ends
+// drained either way; the slot's eh / ed must be free (nothing pending on them).
+int stage_out(HostSlot &sl, void *dst, const void *dev, uint64_t bytes, hipStream_t s) {
+  if (bytes) return d2h_pipelined(dst, sl.pin_out, dev, bytes, s, sl.eh, sl.ed);
+  return hip_ok(hipStreamSynchronize(s));
+}
+
+// the context's pipe with staging of at least the given sizes (grow-only)
 // (nslots: the slots the caller stages through -- the single-slot forms, one
 // message or stream of unknown length, grow slot 0 alone, so a large one
 // does not also pin and allocate the same again in slot 1)
@@ -222,11 +266,13 @@ int small_encode(cpk_ctx ctx, uint64_t np, uint64_t words, Lay lay, void *h_out,
   return CPK_OK;
 }
 
+// A chunk of a host batch: whole pieces, or whole messages
 struct HostChunk {
-  uint32_t i0, i1;       // pieces [i0, i1)
+  uint32_t i0, i1;       // pieces / messages [i0, i1)
+  uint64_t s0, s1;       // messages, encode: their segments [s0, s1) (else 0, 0)
   uint64_t in0, in_len;  // input bytes (encode: words * 8; decode: packed range)
-  uint64_t out_cap;      // output bytes the chunk may produce
-  uint64_t maxw;         // largest piece, words
+  uint64_t out_cap;      // output bytes the chunk may produce (message decode: not known)
+  uint64_t maxw;         // encode: largest piece / segment, words
 };
 
 // chunks of whole pieces, each about `target` bytes of unpacked words (a
@@ -264,21 +310,6 @@ std::vector<HostChunk> host_chunks(const uint64_t *swo, const uint64_t *in_off, 
   return cs;
 }
 
-// wait for everything the pipe has in flight (error paths)
-void pipe_drain(HostPipe *p) {
-  hipStreamSynchronize(p->sh);
-  hipStreamSynchronize(p->sk);
-  hipStreamSynchronize(p->sd);
-}
-
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
-
 // piece j of the chunk is 8 * (swo[j+1] - swo[j]) bytes at pieces[j]; they go
 // back to back into `dst` (pinned staging), split over host threads by bytes
 void gather_copy(uint8_t *dst, const void *const *pieces, const uint64_t *swo, uint32_t i0,
@@ -307,6 +338,130 @@ void gather_copy(uint8_t *dst, const void *const *pieces, const uint64_t *swo, u
   for (auto &t : ts) t.join();
 }
 
+// ---- the chunk pipeline
+// What a form tells run_chunks besides its four callables:
+//   copy_in(pin, c)      chunk c's input bytes into the pinned input slot
+//   meta(slot, c)        c's meta words into slot.pin_meta; -> how many go up
+//   launch(slot, c, sk)  the device call on sk and the D2H, on sk, of the meta
+//                        words it leaves; -> rc
+//   land(slot, c)        once those are back: the caller's offsets or
+//                        statuses; -> where c's output bytes go, or an error
+struct ChunkForm {
+  bool encode;            // the unpacked words are the input (else the output)
+  bool trace;             // CPK_HOST_TRACE write marks (cpk_encode_host[_gather])
+  uint32_t slack;         // zero bytes sent behind a chunk's input (the decoder's read slack)
+  const uint8_t *contig;  // the caller's input where it is one buffer (c.in0 its offset), else null
+  uint64_t (*meta_cap)(const HostChunk &);  // meta words the chunk needs in its slot
+};
+struct ChunkOut {
+  int rc;
+  uint8_t *dst;
+  uint64_t bytes;
+};
+
+// Chunk k is copied in, sent up and launched; chunk k-1's meta words are
+// landed and its D2H issued; chunk k-2 is copied out.
+template <class CopyIn, class Meta, class Launch, class Land>
+int run_chunks(cpk_ctx ctx, const std::vector<HostChunk> &cs, const ChunkForm &f, CopyIn copy_in, Meta meta,
+               Launch launch, Land land) {
+  uint64_t mi = 0, mo = 0, mm = 0;
+  for (const HostChunk &c : cs) {
+    mi = c.in_len > mi ? c.in_len : mi;
+    mo = c.out_cap > mo ? c.out_cap : mo;
+    mm = f.meta_cap(c) > mm ? f.meta_cap(c) : mm;
+  }
+  HostPipe *p = nullptr;
+  int rc = pipe_get(ctx, mi, mo, mm, &p);
+  if (rc) return rc;
+  PipeGuard guard{p};
+  const size_t K = cs.size();
+  TrClock tc(ctx);
+  auto mark = [&](int phase) {
+    if (f.trace) tc.mark(phase);
+  };
+  // one large chunk (e.g. a single big piece or message): nothing to overlap
+  // it with, so its own transfers are pipelined in 16 MiB chunks instead
+  // (stage_in / stage_out; its slot's eh and ed are free by then)
+  const bool one = K == 1 && (f.encode ? cs[0].in_len : cs[0].out_cap) >= 2 * kPipeChunk;
+  bool streamed = false;  // the one chunk's output went out through stage_out
+  ChunkOut out[2] = {};
+  auto send = [&](size_t k) -> int {  // copy-in, H2D, kernels of chunk k
+    const HostChunk &c = cs[k];
+    HostSlot &s = p->slot[k & 1];
+    const uint64_t up = meta(s, c);
+    if (one && f.contig) {
+      if (stage_in(s, f.contig + c.in0, c.in_len, f.slack, p->sh)) return CPK_EDEVICE;
+    } else {
+      copy_in((uint8_t *)s.pin_in, c);
+      memset((uint8_t *)s.pin_in + c.in_len, 0, f.slack);
+      if (c.in_len + f.slack &&
+          hipMemcpyAsync(s.d_in, s.pin_in, c.in_len + f.slack, hipMemcpyHostToDevice, p->sh))
+        return CPK_EDEVICE;
+    }
+    mark(kTrWIn);
+    if (hipMemcpyAsync(s.d_meta, s.pin_meta, up * 8, hipMemcpyHostToDevice, p->sh) ||
+        hipEventRecord(s.eh, p->sh) || hipStreamWaitEvent(p->sk, s.eh, 0) ||
+        (k >= 2 && hipStreamWaitEvent(p->sk, s.ed, 0)))  // (d_out free: chunk k-2's D2H)
+      return CPK_EDEVICE;
+    if (int r = launch(s, c, p->sk)) return r;
+    if (hipEventRecord(s.ek, p->sk)) return CPK_EDEVICE;
+    mark(kTrWLaunch);
+    return CPK_OK;
+  };
+  auto fetch = [&](size_t k) -> int {  // chunk k: offsets / statuses, then its D2H
+    HostSlot &s = p->slot[k & 1];
+    ChunkOut &o = out[k & 1];
+    if (hipEventSynchronize(s.ek)) return CPK_EDEVICE;
+    mark(kTrWWait);
+    o = land(s, cs[k]);
+    if (o.rc) return o.rc;
+    if (one && o.bytes >= 2 * kPipeChunk) {
+      streamed = true;
+      return stage_out(s, o.dst, s.d_out, o.bytes, p->sd);
+    }
+    if ((o.bytes && hipMemcpyAsync(s.pin_out, s.d_out, o.bytes, hipMemcpyDeviceToHost, p->sd)) ||
+        hipEventRecord(s.ed, p->sd))
+      return CPK_EDEVICE;
+    return CPK_OK;
+  };
+  auto copy_out = [&](size_t k) -> int {  // chunk k: copy-out
+    HostSlot &s = p->slot[k & 1];
+    if (hipEventSynchronize(s.ed)) return CPK_EDEVICE;
+    mark(kTrWWait);
+    par_copy(out[k & 1].dst, s.pin_out, out[k & 1].bytes);
+    mark(kTrWOut);
+    return CPK_OK;
+  };
+  for (size_t k = 0; k <= K + 1 && !rc && !streamed; ++k) {
+    if (k < K) rc = send(k);
+    if (!rc && k >= 1 && k <= K) rc = fetch(k - 1);
+    if (!rc && k >= 2 && !streamed) rc = copy_out(k - 2);
+  }
+  if (rc) return rc;
+  guard.done();
+  // (the encoders: a piece over its hint cannot occur, each chunk's hint is
+  // its largest piece)
+  if (f.encode) rc = cpk_ctx_take_error(ctx, p->sk);
+  mark(kTrWWait);
+  return rc;
+}
+
+// The encoders' landing: a chunk's piece offsets (its pieces, or its
+// messages' tables and segments in message order, counted from the chunk's
+// own zero) become the caller's at the running total of packed bytes.
+struct PackedOut {
+  uint8_t *dst;
+  uint64_t cap, *off, base;
+  ChunkOut land(const HostChunk &c, const uint64_t *coff) {
+    const uint64_t np = (c.i1 - c.i0) + (c.s1 - c.s0), P = coff[np];
+    if (P > c.out_cap) return {CPK_EDEVICE, nullptr, 0};  // (cannot happen: a piece over its bound)
+    if (base + P > cap) return {CPK_ENOMEM, nullptr, 0};
+    for (uint64_t j = 0; j <= np; ++j) off[c.i0 + c.s0 + j] = base + coff[j];
+    base += P;
+    return {CPK_OK, dst + base - P, P};
+  }
+};
+
 // cpk_encode_host / cpk_encode_host_gather: `copy_in` fills a chunk's pinned
 // input slot
 template <class CopyIn>
@@ -322,7 +477,7 @@ int encode_host_impl(cpk_ctx ctx, CopyIn copy_in, const uint64_t *h_swo, uint32_
   if (small_ok(h_swo[n] - h_swo[0], n)) {
     // (in0: the words' absolute byte offset in the caller's buffer, as
     // host_chunks sets it; the gather form copies piece by piece)
-    const HostChunk all{0, n, 8 * h_swo[0], 8 * (h_swo[n] - h_swo[0]), 0, 0};
+    const HostChunk all{0, n, 0, 0, 8 * h_swo[0], 8 * (h_swo[n] - h_swo[0]), 0, 0};
     return small_encode(
         ctx, n, h_swo[n] - h_swo[0],
         [&](uint64_t *pin, uint64_t *desc) {
@@ -334,117 +489,24 @@ int encode_host_impl(cpk_ctx ctx, CopyIn copy_in, const uint64_t *h_swo, uint32_
         },
         h_out, h_out_cap, h_out_off, 0);
   }
-  const std::vector<HostChunk> cs = host_chunks(h_swo, nullptr, n, host_chunk_bytes());
-  uint64_t mi = 0, mo = 0, mm = 0;
-  for (const HostChunk &c : cs) {
-    mi = c.in_len > mi ? c.in_len : mi;
-    mo = c.out_cap > mo ? c.out_cap : mo;
-    mm = c.i1 - c.i0 > mm ? c.i1 - c.i0 : mm;
-  }
-  HostPipe *p = nullptr;
-  int rc = pipe_get(ctx, mi, mo, 2 * (mm + 1), &p);
-  if (rc) return rc;
-  uint8_t *dst = (uint8_t *)h_out;
-  uint64_t base = 0;          // output bytes so far
-  const size_t K = cs.size();
-  TrClock tc(ctx);
-  // one large chunk (e.g. a single big piece): nothing to overlap it with,
-  // so its own transfers are pipelined in 16 MiB chunks instead
-  const bool one = K == 1 && cs[0].in_len >= 2 * kPipeChunk;
-  for (size_t k = 0; k <= K + 1 && rc == CPK_OK; ++k) {
-    if (k < K) {  // copy-in, H2D, kernels of chunk k
-      const HostChunk &c = cs[k];
-      HostSlot &s = p->slot[k & 1];
-      const uint32_t nk = c.i1 - c.i0;
-      for (uint32_t j = 0; j <= nk; ++j) s.pin_meta[j] = h_swo[c.i0 + j] - h_swo[c.i0];
-      if (one && contig) {
-        if (h2d_pipelined(s.d_in, s.pin_in, contig + c.in0, c.in_len, p->sh)) {
-          rc = CPK_EDEVICE;
-          break;
-        }
-      } else {
-        copy_in((uint8_t *)s.pin_in, c);
-        if (c.in_len && hipMemcpyAsync(s.d_in, s.pin_in, c.in_len, hipMemcpyHostToDevice, p->sh)) {
-          rc = CPK_EDEVICE;
-          break;
-        }
-      }
-      tc.mark(kTrWIn);
-      if (hipMemcpyAsync(s.d_meta, s.pin_meta, (nk + 1) * 8ull, hipMemcpyHostToDevice, p->sh) ||
-          hipEventRecord(s.eh, p->sh) || hipStreamWaitEvent(p->sk, s.eh, 0) ||
-          (k >= 2 && hipStreamWaitEvent(p->sk, s.ed, 0))) {  // (d_out free: chunk k-2's D2H)
-        rc = CPK_EDEVICE;
-        break;
-      }
-      rc = cpk_encode_batch(ctx, s.d_in, s.d_meta, nk, c.maxw ? c.maxw : 1, s.d_out,
-                            s.d_meta + nk + 1, p->sk);
-      if (rc) break;
-      if (hipMemcpyAsync(s.pin_meta + nk + 1, s.d_meta + nk + 1, (nk + 1) * 8ull,
-                         hipMemcpyDeviceToHost, p->sk) ||
-          hipEventRecord(s.ek, p->sk)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      tc.mark(kTrWLaunch);
-    }
-    if (k >= 1 && k - 1 < K) {  // chunk k-1: offsets, then its D2H
-      const HostChunk &c = cs[k - 1];
-      HostSlot &s = p->slot[(k - 1) & 1];
-      const uint32_t nk = c.i1 - c.i0;
-      if (hipEventSynchronize(s.ek)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      tc.mark(kTrWWait);
-      const uint64_t *off = s.pin_meta + nk + 1;
-      const uint64_t P = off[nk];
-      if (P > c.out_cap) {  // (cannot happen: a piece over its hint)
-        rc = CPK_EDEVICE;
-        break;
-      }
-      if (base + P > h_out_cap) {
-        rc = CPK_ENOMEM;
-        break;
-      }
-      for (uint32_t j = 0; j <= nk; ++j) h_out_off[c.i0 + j] = base + off[j];
-      if (one && P >= 2 * kPipeChunk) {
-        // (the one chunk's copy-out under its own D2H; the events of the
-        // other slot are free)
-        if (d2h_pipelined(dst + base, s.pin_out, s.d_out, P, p->sd, p->slot[1].eh, p->slot[1].ed)) {
-          rc = CPK_EDEVICE;
-          break;
-        }
-        base += P;
-        break;
-      }
-      if ((P && hipMemcpyAsync(s.pin_out, s.d_out, P, hipMemcpyDeviceToHost, p->sd)) ||
-          hipEventRecord(s.ed, p->sd)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      base += P;
-    }
-    if (k >= 2) {  // chunk k-2: copy-out
-      const HostChunk &c = cs[k - 2];
-      HostSlot &s = p->slot[k & 1];
-      if (hipEventSynchronize(s.ed)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      tc.mark(kTrWWait);
-      const uint64_t o0 = h_out_off[c.i0], o1 = h_out_off[c.i1];
-      par_copy(dst + o0, s.pin_out, o1 - o0);
-      tc.mark(kTrWOut);
-    }
-  }
-  if (rc) {
-    pipe_drain(p);
-    return rc;
-  }
-  // (a piece over its hint cannot occur: each chunk's hint is its largest piece)
-  rc = cpk_ctx_take_error(ctx, p->sk);
-  tc.mark(kTrWWait);
-  return rc;
+  PackedOut po{(uint8_t *)h_out, h_out_cap, h_out_off, 0};
+  // meta: swo [nk + 1] | out_off [nk + 1]
+  return run_chunks(
+      ctx, host_chunks(h_swo, nullptr, n, host_chunk_bytes()),
+      ChunkForm{true, true, 0, contig, [](const HostChunk &c) -> uint64_t { return 2 * (c.i1 - c.i0 + 1ull); }},
+      copy_in,
+      [&](HostSlot &s, const HostChunk &c) {
+        const uint32_t nk = c.i1 - c.i0;
+        for (uint32_t j = 0; j <= nk; ++j) s.pin_meta[j] = h_swo[c.i0 + j] - h_swo[c.i0];
+        return nk + 1ull;
+      },
+      [&](HostSlot &s, const HostChunk &c, hipStream_t sk) {
+        const uint32_t nk = c.i1 - c.i0;
+        uint64_t *doff = s.d_meta + nk + 1;
+        if (int rc = cpk_encode_batch(ctx, s.d_in, s.d_meta, nk, c.maxw ? c.maxw : 1, s.d_out, doff, sk)) return rc;
+        return hip_ok(hipMemcpyAsync(s.pin_meta + nk + 1, doff, (nk + 1) * 8ull, hipMemcpyDeviceToHost, sk));
+      },
+      [&](HostSlot &s, const HostChunk &c) { return po.land(c, s.pin_meta + (c.i1 - c.i0) + 1); });
 }
 
 }  // namespace
@@ -504,98 +566,33 @@ int cpk_decode_host(cpk_ctx ctx, const void *h_packed, const uint64_t *h_in_off,
       }
     }
   }
-  const std::vector<HostChunk> cs = host_chunks(h_swo, h_in_off, n, host_chunk_bytes());
-  uint64_t mi = 0, mo = 0, mm = 0;
-  for (const HostChunk &c : cs) {
-    mi = c.in_len > mi ? c.in_len : mi;
-    mo = c.out_cap > mo ? c.out_cap : mo;
-    mm = c.i1 - c.i0 > mm ? c.i1 - c.i0 : mm;
-  }
-  HostPipe *p = nullptr;
-  // meta: swo | in_off | status (int32, n/2 + 1 entries)
-  int rc = pipe_get(ctx, mi, mo, 2 * (mm + 1) + mm / 2 + 1, &p);
-  if (rc) return rc;
   const uint8_t *src = (const uint8_t *)h_packed;
-  uint8_t *dst = (uint8_t *)h_out;
-  const size_t K = cs.size();
-  // one large chunk (a single big piece): its own transfers pipelined in
-  // 16 MiB chunks (encode_host_impl likewise)
-  const bool one = K == 1 && cs[0].out_cap >= 2 * kPipeChunk;
-  for (size_t k = 0; k <= K + 1 && rc == CPK_OK; ++k) {
-    if (k < K) {  // copy-in, H2D, decode of chunk k
-      const HostChunk &c = cs[k];
-      HostSlot &s = p->slot[k & 1];
-      const uint32_t nk = c.i1 - c.i0;
-      memset((uint8_t *)s.pin_in + c.in_len, 0, 32);  // (the decoder reads whole 16-byte lines)
-      for (uint32_t j = 0; j <= nk; ++j) {
-        s.pin_meta[j] = h_swo[c.i0 + j] - h_swo[c.i0];
-        s.pin_meta[nk + 1 + j] = h_in_off[c.i0 + j] - h_in_off[c.i0];
-      }
-      int32_t *st = (int32_t *)(s.d_meta + 2 * (nk + 1));
-      if (one) {
-        if (h2d_pipelined(s.d_in, s.pin_in, src + c.in0, c.in_len, p->sh) ||
-            hipMemcpyAsync((uint8_t *)s.d_in + c.in_len, (uint8_t *)s.pin_in + c.in_len, 32, hipMemcpyHostToDevice,
-                           p->sh)) {
-          rc = CPK_EDEVICE;
-          break;
+  // meta: swo [nk + 1] | in_off [nk + 1] | status (int32, nk / 2 + 1 entries)
+  const int rc = run_chunks(
+      ctx, host_chunks(h_swo, h_in_off, n, host_chunk_bytes()),
+      ChunkForm{false, false, 32, src,  // (the decoder reads whole 16-byte lines)
+                [](const HostChunk &c) -> uint64_t { return 2 * (c.i1 - c.i0 + 1ull) + (c.i1 - c.i0) / 2 + 1; }},
+      [&](uint8_t *pin, const HostChunk &c) { par_copy(pin, src + c.in0, c.in_len); },
+      [&](HostSlot &s, const HostChunk &c) {
+        const uint32_t nk = c.i1 - c.i0;
+        for (uint32_t j = 0; j <= nk; ++j) {
+          s.pin_meta[j] = h_swo[c.i0 + j] - h_swo[c.i0];
+          s.pin_meta[nk + 1 + j] = h_in_off[c.i0 + j] - h_in_off[c.i0];
         }
-      } else {
-        par_copy(s.pin_in, src + c.in0, c.in_len);
-        if (hipMemcpyAsync(s.d_in, s.pin_in, c.in_len + 32, hipMemcpyHostToDevice, p->sh)) {
-          rc = CPK_EDEVICE;
-          break;
-        }
-      }
-      if (hipMemcpyAsync(s.d_meta, s.pin_meta, 2 * (nk + 1) * 8ull, hipMemcpyHostToDevice, p->sh) ||
-          hipEventRecord(s.eh, p->sh) || hipStreamWaitEvent(p->sk, s.eh, 0) ||
-          (k >= 2 && hipStreamWaitEvent(p->sk, s.ed, 0))) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      rc = decode_batch_impl(ctx, s.d_in, s.d_meta + nk + 1, s.d_meta, nk, s.d_out, st, p->sk, false);
-      if (rc) break;
-      if (hipMemcpyAsync(s.pin_meta + 2 * (nk + 1), st, nk * 4ull, hipMemcpyDeviceToHost, p->sk) ||
-          hipEventRecord(s.ek, p->sk)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-    }
-    if (k >= 1 && k - 1 < K) {  // chunk k-1: statuses, then its D2H
-      const HostChunk &c = cs[k - 1];
-      HostSlot &s = p->slot[(k - 1) & 1];
-      const uint32_t nk = c.i1 - c.i0;
-      if (hipEventSynchronize(s.ek)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      memcpy(h_status + c.i0, s.pin_meta + 2 * (nk + 1), nk * 4ull);
-      if (one) {
-        // (its copy-out under its own D2H; the other slot's events are free)
-        if (d2h_pipelined(dst + 8 * h_swo[c.i0], s.pin_out, s.d_out, c.out_cap, p->sd, p->slot[1].eh,
-                          p->slot[1].ed))
-          rc = CPK_EDEVICE;
-        break;
-      }
-      if ((c.out_cap && hipMemcpyAsync(s.pin_out, s.d_out, c.out_cap, hipMemcpyDeviceToHost, p->sd)) ||
-          hipEventRecord(s.ed, p->sd)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-    }
-    if (k >= 2) {  // chunk k-2: copy-out
-      const HostChunk &c = cs[k - 2];
-      HostSlot &s = p->slot[k & 1];
-      if (hipEventSynchronize(s.ed)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      par_copy(dst + 8 * h_swo[c.i0], s.pin_out, c.out_cap);
-    }
-  }
-  if (rc) {
-    pipe_drain(p);
-    return rc;
-  }
+        return 2 * (nk + 1ull);
+      },
+      [&](HostSlot &s, const HostChunk &c, hipStream_t sk) {
+        const uint32_t nk = c.i1 - c.i0;
+        int32_t *st = (int32_t *)(s.d_meta + 2 * (nk + 1ull));
+        if (int r = decode_batch_impl(ctx, s.d_in, s.d_meta + nk + 1, s.d_meta, nk, s.d_out, st, sk, false)) return r;
+        return hip_ok(hipMemcpyAsync(s.pin_meta + 2 * (nk + 1ull), st, nk * 4ull, hipMemcpyDeviceToHost, sk));
+      },
+      [&](HostSlot &s, const HostChunk &c) {
+        const uint32_t nk = c.i1 - c.i0;
+        memcpy(h_status + c.i0, s.pin_meta + 2 * (nk + 1ull), nk * 4ull);
+        return ChunkOut{CPK_OK, (uint8_t *)h_out + 8 * h_swo[c.i0], c.out_cap};
+      });
+  if (rc) return rc;
   for (uint32_t i = 0; i < n; ++i)
     if (h_status[i] != CPK_OK) return h_status[i];
   return CPK_OK;
@@ -608,24 +605,16 @@ int cpk_decode_host(cpk_ctx ctx, const void *h_packed, const uint64_t *h_in_off,
 // whole messages through the same two pinned slots as the piece forms
 namespace {
 
-struct MsgChunk {
-  uint32_t m0, m1;    // messages [m0, m1)
-  uint64_t s0, s1;    // their segments (encode) / none (decode)
-  uint64_t in0, in_len;  // input bytes: segment words (encode) / packed (decode)
-  uint64_t out_cap;   // encode: packed bytes the chunk may produce
-  uint64_t maxw;      // encode: largest segment, words
-};
-
 // encode: chunks of about `target` bytes of segment words
-std::vector<MsgChunk> enc_msg_chunks(const uint64_t *swo, const uint64_t *mso, uint32_t nm, uint64_t target) {
-  std::vector<MsgChunk> cs;
+std::vector<HostChunk> enc_msg_chunks(const uint64_t *swo, const uint64_t *mso, uint32_t nm, uint64_t target) {
+  std::vector<HostChunk> cs;
   uint32_t m = 0;
   while (m < nm) {
-    MsgChunk c{m, m, mso[m], mso[m], 0, 0, 16, 1};
-    while (c.m1 < nm) {
-      const uint64_t a = mso[c.m1], b = mso[c.m1 + 1];
+    HostChunk c{m, m, mso[m], mso[m], 0, 0, 16, 1};
+    while (c.i1 < nm) {
+      const uint64_t a = mso[c.i1], b = mso[c.i1 + 1];
       const uint64_t bytes = 8 * (swo[b] - swo[a]);
-      if (c.m1 > c.m0 && c.in_len + bytes > target) break;
+      if (c.i1 > c.i0 && c.in_len + bytes > target) break;
       c.in_len += bytes;
       for (uint64_t i = a; i < b; ++i) {
         const uint64_t w = swo[i + 1] - swo[i];
@@ -633,12 +622,12 @@ std::vector<MsgChunk> enc_msg_chunks(const uint64_t *swo, const uint64_t *mso, u
         c.maxw = w > c.maxw ? w : c.maxw;
       }
       c.out_cap += 10 * ((b - a + 2) / 2 + 1);
-      ++c.m1;
+      ++c.i1;
     }
-    c.s1 = mso[c.m1];
+    c.s1 = mso[c.i1];
     c.in0 = 8 * (swo[c.s0] - swo[0]);
     cs.push_back(c);
-    m = c.m1;
+    m = c.i1;
   }
   return cs;
 }
@@ -671,7 +660,7 @@ int encode_messages_host_impl(cpk_ctx ctx, Fill fill, const uint64_t *h_swo, uin
       return small_encode(
           ctx, np, sw + tw,
           [&](uint64_t *pin, uint64_t *desc) {
-            if (sw) fill((uint8_t *)pin, MsgChunk{0, nm, 0, nseg, 0, 8 * sw, 0, 0});
+            if (sw) fill((uint8_t *)pin, HostChunk{0, nm, 0, nseg, 0, 8 * sw, 0, 0});
             uint64_t t = sw, q = 0;
             for (uint32_t m = 0; m < nm; ++m) {
               const uint64_t a = h_msg_seg_off[m], b = h_msg_seg_off[m + 1];
@@ -697,114 +686,31 @@ int encode_messages_host_impl(cpk_ctx ctx, Fill fill, const uint64_t *h_swo, uin
           },
           h_out, h_out_cap, h_out_off, 0);
   }
-  const std::vector<MsgChunk> cs = enc_msg_chunks(h_swo, h_msg_seg_off, nm, host_chunk_bytes());
-  uint64_t mi = 0, mo = 0, mm = 0;
-  for (const MsgChunk &c : cs) {
-    const uint64_t ns = c.s1 - c.s0, nmk = c.m1 - c.m0;
-    mi = c.in_len > mi ? c.in_len : mi;
-    mo = c.out_cap > mo ? c.out_cap : mo;
-    // meta: swo [ns + 1] | msg_seg_off [nm + 1] | out_off [nm + ns + 1]
-    const uint64_t need = (ns + 1) + (nmk + 1) + (nmk + ns + 1);
-    mm = need > mm ? need : mm;
-  }
-  HostPipe *p = nullptr;
-  int rc = pipe_get(ctx, mi, mo, mm, &p);
-  if (rc) return rc;
-  uint8_t *dst = (uint8_t *)h_out;
-  uint64_t base = 0;
-  const size_t K = cs.size();
-  // one large chunk (e.g. one big message): its own transfers pipelined in
-  // 16 MiB sub-chunks (encode_host_impl likewise)
-  const bool one = K == 1 && cs[0].in_len >= 2 * kPipeChunk;
-  for (size_t k = 0; k <= K + 1 && rc == CPK_OK; ++k) {
-    if (k < K) {  // copy-in, H2D, kernels of chunk k
-      const MsgChunk &c = cs[k];
-      HostSlot &s = p->slot[k & 1];
-      const uint32_t ns = (uint32_t)(c.s1 - c.s0), nmk = c.m1 - c.m0;
-      uint64_t *m = s.pin_meta;
-      for (uint32_t j = 0; j <= ns; ++j) m[j] = h_swo[c.s0 + j] - h_swo[c.s0];
-      for (uint32_t j = 0; j <= nmk; ++j) m[ns + 1 + j] = h_msg_seg_off[c.m0 + j] - c.s0;
-      uint64_t *dm = s.d_meta, *doff = dm + (ns + 1) + (nmk + 1);
-      if (one && contig) {
-        if (h2d_pipelined(s.d_in, s.pin_in, contig + c.in0, c.in_len, p->sh)) {
-          rc = CPK_EDEVICE;
-          break;
-        }
-      } else {
-        fill((uint8_t *)s.pin_in, c);
-        if (c.in_len && hipMemcpyAsync(s.d_in, s.pin_in, c.in_len, hipMemcpyHostToDevice, p->sh)) {
-          rc = CPK_EDEVICE;
-          break;
-        }
-      }
-      if (hipMemcpyAsync(dm, m, ((ns + 1) + (nmk + 1)) * 8ull, hipMemcpyHostToDevice, p->sh) ||
-          hipEventRecord(s.eh, p->sh) || hipStreamWaitEvent(p->sk, s.eh, 0) ||
-          (k >= 2 && hipStreamWaitEvent(p->sk, s.ed, 0))) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      rc = cpk_encode_messages(ctx, s.d_in, dm, ns, dm + ns + 1, nmk, c.maxw, s.d_out, doff, p->sk);
-      if (rc) break;
-      if (hipMemcpyAsync(m + (ns + 1) + (nmk + 1), doff, ((uint64_t)nmk + ns + 1) * 8, hipMemcpyDeviceToHost,
-                         p->sk) ||
-          hipEventRecord(s.ek, p->sk)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-    }
-    if (k >= 1 && k - 1 < K) {  // chunk k-1: offsets, then its D2H
-      const MsgChunk &c = cs[k - 1];
-      HostSlot &s = p->slot[(k - 1) & 1];
-      const uint32_t ns = (uint32_t)(c.s1 - c.s0), nmk = c.m1 - c.m0;
-      if (hipEventSynchronize(s.ek)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      const uint64_t *off = s.pin_meta + (ns + 1) + (nmk + 1);
-      const uint64_t np = (uint64_t)nmk + ns, P = off[np];
-      if (P > c.out_cap) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      if (base + P > h_out_cap) {
-        rc = CPK_ENOMEM;
-        break;
-      }
-      // pieces in message order: chunk k-1's start at piece c.m0 + c.s0
-      for (uint64_t j = 0; j <= np; ++j) h_out_off[c.m0 + c.s0 + j] = base + off[j];
-      if (one && P >= 2 * kPipeChunk) {
-        // (the one chunk's copy-out under its own D2H; the other slot's events are free)
-        if (d2h_pipelined(dst + base, s.pin_out, s.d_out, P, p->sd, p->slot[1].eh, p->slot[1].ed)) {
-          rc = CPK_EDEVICE;
-          break;
-        }
-        base += P;
-        break;
-      }
-      if ((P && hipMemcpyAsync(s.pin_out, s.d_out, P, hipMemcpyDeviceToHost, p->sd)) ||
-          hipEventRecord(s.ed, p->sd)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      base += P;
-    }
-    if (k >= 2) {  // chunk k-2: copy-out
-      const MsgChunk &c = cs[k - 2];
-      HostSlot &s = p->slot[k & 1];
-      if (hipEventSynchronize(s.ed)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
-      const uint64_t np = (uint64_t)(c.m1 - c.m0) + (c.s1 - c.s0);
-      const uint64_t o0 = h_out_off[c.m0 + c.s0], o1 = h_out_off[c.m0 + c.s0 + np];
-      par_copy(dst + o0, s.pin_out, o1 - o0);
-    }
-  }
-  if (rc) {
-    pipe_drain(p);
-    return rc;
-  }
-  return cpk_ctx_take_error(ctx, p->sk);
+  PackedOut po{(uint8_t *)h_out, h_out_cap, h_out_off, 0};
+  // meta: swo [ns + 1] | msg_seg_off [nmk + 1] | out_off [nmk + ns + 1]
+  auto up_words = [](const HostChunk &c) -> uint64_t { return (c.s1 - c.s0 + 1) + (c.i1 - c.i0 + 1ull); };
+  return run_chunks(
+      ctx, enc_msg_chunks(h_swo, h_msg_seg_off, nm, host_chunk_bytes()),
+      ChunkForm{true, false, 0, contig,
+                [](const HostChunk &c) -> uint64_t {
+                  const uint64_t ns = c.s1 - c.s0, nmk = c.i1 - c.i0;
+                  return (ns + 1) + (nmk + 1) + (nmk + ns + 1);
+                }},
+      fill,
+      [&](HostSlot &s, const HostChunk &c) {
+        const uint32_t ns = (uint32_t)(c.s1 - c.s0), nmk = c.i1 - c.i0;
+        for (uint32_t j = 0; j <= ns; ++j) s.pin_meta[j] = h_swo[c.s0 + j] - h_swo[c.s0];
+        for (uint32_t j = 0; j <= nmk; ++j) s.pin_meta[ns + 1 + j] = h_msg_seg_off[c.i0 + j] - c.s0;
+        return up_words(c);
+      },
+      [&](HostSlot &s, const HostChunk &c, hipStream_t sk) {
+        const uint32_t ns = (uint32_t)(c.s1 - c.s0), nmk = c.i1 - c.i0;
+        uint64_t *dm = s.d_meta, *doff = dm + up_words(c);
+        if (int rc = cpk_encode_messages(ctx, s.d_in, dm, ns, dm + ns + 1, nmk, c.maxw, s.d_out, doff, sk)) return rc;
+        return hip_ok(hipMemcpyAsync(s.pin_meta + up_words(c), doff, ((uint64_t)nmk + ns + 1) * 8,
+                                     hipMemcpyDeviceToHost, sk));
+      },
+      [&](HostSlot &s, const HostChunk &c) { return po.land(c, s.pin_meta + up_words(c)); });
 }
 
 }  // namespace
@@ -817,7 +723,7 @@ int cpk_encode_messages_host(cpk_ctx ctx, const void *h_in, const uint64_t *h_sw
   if (!h_swo || (nseg && h_swo[nseg] > h_swo[0] && !h_in) || (nm && !h_out)) return CPK_EINVAL;
   const uint8_t *src = (const uint8_t *)h_in + 8 * h_swo[0];
   return encode_messages_host_impl(
-      ctx, [&](uint8_t *pin, const MsgChunk &c) { par_copy(pin, src + c.in0, c.in_len); }, h_swo, nseg,
+      ctx, [&](uint8_t *pin, const HostChunk &c) { par_copy(pin, src + c.in0, c.in_len); }, h_swo, nseg,
       h_msg_seg_off, nm, h_out, h_out_cap, h_out_off, src);
 }
 
@@ -829,7 +735,7 @@ int cpk_encode_messages_host_gather(cpk_ctx ctx, const void *const *h_segs, cons
     if (h_swo[i + 1] > h_swo[i] && !h_segs[i]) return CPK_EINVAL;
   return encode_messages_host_impl(
       ctx,
-      [&](uint8_t *pin, const MsgChunk &c) {
+      [&](uint8_t *pin, const HostChunk &c) {
         gather_copy(pin, h_segs, h_swo, (uint32_t)c.s0, (uint32_t)c.s1);
       },
       h_swo, nseg, h_msg_seg_off, nm, h_out, h_out_cap, h_out_off);
@@ -856,18 +762,18 @@ int cpk_decode_messages_host(cpk_ctx ctx, const void *h_packed, const uint64_t *
   DeviceGuard g(ctx->device);
   // chunks of whole messages, about `target` packed bytes each
   const uint64_t target = host_chunk_bytes() / 2;
-  std::vector<MsgChunk> cs;
+  std::vector<HostChunk> cs;
   for (uint32_t m = 0; m < nm;) {
-    MsgChunk c{m, m, 0, 0, h_msg_off[m], 0, 0, 0};
-    while (c.m1 < nm && (c.m1 == c.m0 || h_msg_off[c.m1 + 1] - c.in0 <= target)) ++c.m1;
-    c.in_len = h_msg_off[c.m1] - c.in0;
+    HostChunk c{m, m, 0, 0, h_msg_off[m], 0, 0, 0};
+    while (c.i1 < nm && (c.i1 == c.i0 || h_msg_off[c.i1 + 1] - c.in0 <= target)) ++c.i1;
+    c.in_len = h_msg_off[c.i1] - c.in0;
     cs.push_back(c);
-    m = c.m1;
+    m = c.i1;
   }
   uint64_t mi = 0, mmsg = 0;
-  for (const MsgChunk &c : cs) {
+  for (const HostChunk &c : cs) {
     mi = c.in_len > mi ? c.in_len : mi;
-    mmsg = (uint64_t)(c.m1 - c.m0) > mmsg ? c.m1 - c.m0 : mmsg;
+    mmsg = (uint64_t)(c.i1 - c.i0) > mmsg ? c.i1 - c.i0 : mmsg;
   }
   // meta: msg_off [n + 1] | msg_seg_off [n + 1] | msg_status [n] (as u32 pairs)
   //       | seg_word_off [S + 1] | seg_in_off [S + 1] | seg_status [S]
@@ -875,70 +781,61 @@ int cpk_decode_messages_host(cpk_ctx ctx, const void *h_packed, const uint64_t *
   HostPipe *p = nullptr;
   int rc = pipe_get(ctx, mi, 64, meta_need(mmsg, 0), &p);
   if (rc) return rc;
+  PipeGuard guard{p};
   const uint8_t *src = (const uint8_t *)h_packed;
   uint64_t W = 0, S = 0;  // running totals
   bool sizing = false;     // capacities exceeded: table passes only
   int first_bad = CPK_OK;
-  for (size_t k = 0; k < cs.size() && rc == CPK_OK; ++k) {
-    const MsgChunk &c = cs[k];
-    const uint32_t nmk = c.m1 - c.m0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
+  auto decode_chunk = [&](size_t k) -> int {
+    const HostChunk &c = cs[k];
+    const uint32_t nmk = c.i1 - c.i0;
+    for (int attempt = 0;; ++attempt) {
       HostSlot &s = p->slot[k & 1];
-      par_copy(s.pin_in, src + c.in0, c.in_len);
-      memset((uint8_t *)s.pin_in + c.in_len, 0, 64);  // (the decoder reads whole 16-byte lines)
       uint64_t *m = s.pin_meta, *dm = s.d_meta;
-      for (uint32_t j = 0; j <= nmk; ++j) m[j] = h_msg_off[c.m0 + j] - c.in0;
+      for (uint32_t j = 0; j <= nmk; ++j) m[j] = h_msg_off[c.i0 + j] - c.in0;
       uint64_t *d_ms = dm + (nmk + 1);
       int32_t *d_mst = (int32_t *)(d_ms + (nmk + 1));
       uint64_t *d_sw = dm + 2 * (nmk + 1) + (nmk + 1) / 2;
       uint64_t tot[2] = {0, 0};
-      if (hipMemcpyAsync(s.d_in, s.pin_in, c.in_len + 64, hipMemcpyHostToDevice, p->sk) ||
-          hipMemcpyAsync(dm, m, (nmk + 1) * 8ull, hipMemcpyHostToDevice, p->sk)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
+      if (stage_in(s, src + c.in0, c.in_len, 64, p->sk) ||  // (the decoder reads whole 16-byte lines)
+          hipMemcpyAsync(dm, m, (nmk + 1) * 8ull, hipMemcpyHostToDevice, p->sk))
+        return CPK_EDEVICE;
       // the table pass (synchronises the stream for the chunk's totals)
-      rc = cpk_decode_messages(ctx, s.d_in, dm, nmk, traversal_limit_words, nullptr, 0, nullptr, nullptr, nullptr,
-                               0, d_ms, d_mst, tot, p->sk);
-      if (rc == CPK_ENOMEM) rc = CPK_OK;
-      if (rc) break;
+      int r = cpk_decode_messages(ctx, s.d_in, dm, nmk, traversal_limit_words, nullptr, 0, nullptr, nullptr, nullptr,
+                                  0, d_ms, d_mst, tot, p->sk);
+      if (r && r != CPK_ENOMEM) return r;
       if (!sizing && (W + tot[0] > out_cap_words || S + tot[1] > seg_cap || (tot[1] && (!h_out || !h_seg_word_off))))
         sizing = true;
       if (sizing) {
         W += tot[0];
         S += tot[1];
-        break;
+        return CPK_OK;
       }
       // room in the slot for the chunk's words and segments?
       if (tot[0] * 8 + 64 > s.cap_out || meta_need(nmk, tot[1]) > s.cap_meta) {
-        if (attempt) {
-          rc = CPK_EDEVICE;
-          break;
-        }
+        if (attempt) return CPK_EDEVICE;
         pipe_drain(p);
-        rc = pipe_get(ctx, mi, tot[0] * 8, meta_need(mmsg, tot[1]), &p);
-        if (rc) break;  // (no pinned slots left: report it, stage nothing)
-        continue;       // (buffers replaced: stage the chunk again)
+        r = pipe_get(ctx, mi, tot[0] * 8, meta_need(mmsg, tot[1]), &p);
+        if (r) return r;  // (no pinned slots left: report it, stage nothing)
+        continue;         // (buffers replaced: stage the chunk again)
       }
       uint64_t *d_si = d_sw + (tot[1] + 1);
       int32_t *d_ss = (int32_t *)(d_si + (tot[1] + 1));
-      rc = cpk_decode_messages(ctx, s.d_in, dm, nmk, traversal_limit_words, s.d_out, tot[0], d_sw, d_si, d_ss,
-                               (uint32_t)tot[1], d_ms, d_mst, tot, p->sk);
-      if (rc) break;
+      r = cpk_decode_messages(ctx, s.d_in, dm, nmk, traversal_limit_words, s.d_out, tot[0], d_sw, d_si, d_ss,
+                              (uint32_t)tot[1], d_ms, d_mst, tot, p->sk);
+      if (r) return r;
       uint64_t *hm = m + (nmk + 1);  // msg_seg_off | msg_status | seg_word_off
       if (hipMemcpyAsync(hm, d_ms, ((nmk + 1) + (nmk + 1) / 2 + (tot[1] + 1)) * 8ull, hipMemcpyDeviceToHost,
                          p->sk) ||
           (tot[0] && hipMemcpyAsync(s.pin_out, s.d_out, tot[0] * 8, hipMemcpyDeviceToHost, p->sk)) ||
-          hipStreamSynchronize(p->sk)) {
-        rc = CPK_EDEVICE;
-        break;
-      }
+          hipStreamSynchronize(p->sk))
+        return CPK_EDEVICE;
       const uint64_t *ms = hm;
       const int32_t *mst = (const int32_t *)(hm + (nmk + 1));
       const uint64_t *sw = hm + (nmk + 1) + (nmk + 1) / 2;
       for (uint32_t j = 0; j < nmk; ++j) {
-        h_msg_seg_off[c.m0 + j] = S + ms[j];
-        h_msg_status[c.m0 + j] = mst[j];
+        h_msg_seg_off[c.i0 + j] = S + ms[j];
+        h_msg_status[c.i0 + j] = mst[j];
         if (mst[j] != CPK_OK && first_bad == CPK_OK) first_bad = mst[j];
       }
       // (a chunk of broken messages has no segments: the sizing call, with no
@@ -948,13 +845,12 @@ int cpk_decode_messages_host(cpk_ctx ctx, const void *h_packed, const uint64_t *
       if (tot[0]) par_copy((uint8_t *)h_out + 8 * W, s.pin_out, tot[0] * 8);
       W += tot[0];
       S += tot[1];
-      break;
+      return CPK_OK;
     }
-  }
-  if (rc) {
-    pipe_drain(p);
-    return rc;
-  }
+  };
+  for (size_t k = 0; k < cs.size() && rc == CPK_OK; ++k) rc = decode_chunk(k);
+  if (rc) return rc;
+  guard.done();
   h_msg_seg_off[nm] = S;
   h_totals[0] = W;
   h_totals[1] = S;
@@ -962,14 +858,10 @@ int cpk_decode_messages_host(cpk_ctx ctx, const void *h_packed, const uint64_t *
   return first_bad;
 }
 
-}  // extern "C"
-
 // A whole stream of packed messages from host memory
 // (cpk_decode_message_stream): the bytes staged through the pinned slot 0 as
 // cpk_decode_stream_host stages them, the device call, then the complete
 // messages' words and the four arrays copied back.
-extern "C" {
-
 int cpk_decode_message_stream_host(cpk_ctx ctx, const void *h_packed, uint64_t avail,
                                    uint64_t traversal_limit_words, void *h_out, uint64_t out_cap_words,
                                    uint64_t *h_msg_off, uint64_t *h_msg_seg_off, uint32_t msg_cap,
@@ -990,27 +882,20 @@ int cpk_decode_message_stream_host(cpk_ctx ctx, const void *h_packed, uint64_t a
   HostPipe *p = nullptr;
   int rc = pipe_get(ctx, avail, out_cap_words * 8, 2 * mc + 2 * sc + 1, &p, 1);
   if (rc) return rc;
+  PipeGuard guard{p};
   HostSlot &sl = p->slot[0];
   uint64_t *m = sl.pin_meta, *dm = sl.d_meta;
-  memset((uint8_t *)sl.pin_in + avail, 0, 64);  // (the decoder's read slack)
-  if (h2d_pipelined(sl.d_in, sl.pin_in, h_packed, avail, p->sk) ||
-      hipMemcpyAsync((uint8_t *)sl.d_in + avail, (uint8_t *)sl.pin_in + avail, 64, hipMemcpyHostToDevice, p->sk))
-    return CPK_EDEVICE;
+  if (stage_in(sl, h_packed, avail, 64, p->sk)) return CPK_EDEVICE;  // (64: the decoder's read slack)
   rc = cpk_decode_message_stream(ctx, sl.d_in, avail, traversal_limit_words, sl.d_out, out_cap_words,
                                  marr ? dm : nullptr, marr ? dm + mc : nullptr, marr ? msg_cap : 0,
                                  sarr ? dm + 2 * mc : nullptr, sarr ? dm + 2 * mc + sc : nullptr, sarr ? seg_cap : 0,
                                  h_info, p->sk);
-  if (rc) {
-    pipe_drain(p);
-    return rc;
-  }
+  if (rc) return rc;
   const uint64_t nm = h_info[0], ns = h_info[1], words = h_info[2];
-  if (hipMemcpyAsync(m, dm, (2 * mc + 2 * sc) * 8ull, hipMemcpyDeviceToHost, p->sk)) return CPK_EDEVICE;
-  if (words) {
-    if (d2h_pipelined(h_out, sl.pin_out, sl.d_out, words * 8, p->sk, sl.eh, sl.ed)) return CPK_EDEVICE;
-  } else if (hipStreamSynchronize(p->sk)) {
+  if (hipMemcpyAsync(m, dm, (2 * mc + 2 * sc) * 8ull, hipMemcpyDeviceToHost, p->sk) ||
+      stage_out(sl, h_out, sl.d_out, words * 8, p->sk))
     return CPK_EDEVICE;
-  }
+  guard.done();
   if (marr) {
     memcpy(h_msg_off, m, (nm + 1) * 8);
     memcpy(h_msg_seg_off, m + mc, (nm + 1) * 8);
@@ -1046,23 +931,19 @@ int cpk_encode_message_stream_host(cpk_ctx ctx, const void *h_in, uint64_t avail
   HostPipe *p = nullptr;
   int rc = pipe_get(ctx, avail_words * 8, out_cap, pc + mc + 1, &p, 1);
   if (rc) return rc;
+  PipeGuard guard{p};
   HostSlot &sl = p->slot[0];
   uint64_t *m = sl.pin_meta, *dm = sl.d_meta;
-  if (h2d_pipelined(sl.d_in, sl.pin_in, h_in, avail_words * 8, p->sk)) return CPK_EDEVICE;
+  if (stage_in(sl, h_in, avail_words * 8, 0, p->sk)) return CPK_EDEVICE;
   rc = cpk_encode_message_stream(ctx, sl.d_in, avail_words, traversal_limit_words, out_cap ? sl.d_out : nullptr,
                                  out_cap, pc ? dm : nullptr, pc ? piece_cap : 0, mc ? dm + pc : nullptr,
                                  mc ? msg_cap : 0, h_info, p->sk);
-  if (rc) {
-    pipe_drain(p);
-    return rc;
-  }
+  if (rc) return rc;
   const uint64_t nm = h_info[0], np = h_info[1], bytes = h_info[3];
-  if (hipMemcpyAsync(m, dm, (pc + mc) * 8ull, hipMemcpyDeviceToHost, p->sk)) return CPK_EDEVICE;
-  if (bytes) {
-    if (d2h_pipelined(h_out, sl.pin_out, sl.d_out, bytes, p->sk, sl.eh, sl.ed)) return CPK_EDEVICE;
-  } else if (hipStreamSynchronize(p->sk)) {
+  if (hipMemcpyAsync(m, dm, (pc + mc) * 8ull, hipMemcpyDeviceToHost, p->sk) ||
+      stage_out(sl, h_out, sl.d_out, bytes, p->sk))
     return CPK_EDEVICE;
-  }
+  guard.done();
   if (pc) memcpy(h_out_off, m, (np + 1) * 8);
   if (mc) memcpy(h_msg_piece, m + pc, (nm + 1) * 8);
   return CPK_OK;
