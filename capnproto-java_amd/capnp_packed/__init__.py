@@ -40,6 +40,8 @@ EXPORTS = [
     "cpk_encode_batch_cap", "cpk_encode_messages_cap", "cpk_ctx_dense_windows",
     "cpk_decode_message_stream", "cpk_decode_message_stream_host",
     "cpk_encode_message_stream", "cpk_encode_message_stream_host",
+    "cpk_packed_size_batch", "cpk_packed_size_messages", "cpk_packed_size_host",
+    "cpk_packed_size_messages_host",
 ]
 MSG_HEAD_WORDS, MSG_INFO_WORDS = 257, 517  # CPK_MSG_HEAD_WORDS, CPK_MSG_INFO_WORDS
 MS_INFO_WORDS = 5  # CPK_MS_INFO_WORDS
@@ -115,6 +117,10 @@ def load(path: Path | None = None, strict: bool = True) -> ctypes.CDLL:
         "cpk_decode_message_stream_host": ([vp, vp, u64, u64, vp, u64, vp, vp, u32, vp, vp, u32, vp], i32),
         "cpk_encode_message_stream": ([vp, vp, u64, u64, vp, u64, vp, u32, vp, u32, vp, vp], i32),
         "cpk_encode_message_stream_host": ([vp, vp, u64, u64, vp, u64, vp, u32, vp, u32, vp], i32),
+        "cpk_packed_size_batch": ([vp, vp, vp, u32, u64, vp, vp], i32),
+        "cpk_packed_size_messages": ([vp, vp, vp, u32, vp, u32, u64, vp, vp], i32),
+        "cpk_packed_size_host": ([vp, vp, vp, u32, vp], i32),
+        "cpk_packed_size_messages_host": ([vp, vp, vp, u32, vp, u32, vp], i32),
     }
     for name, (args, res) in sig.items():
         if not strict and not hasattr(L, name):
@@ -611,6 +617,63 @@ def _encode_message_stream_host(self, words_or_bytes, traversal_limit_words: int
 
 Context.encode_message_stream = _encode_message_stream
 Context.encode_message_stream_host = _encode_message_stream_host
+
+
+def _packed_size_batch(self, d_in, d_seg_word_off, max_seg_words: int, d_out_off, stream=None):
+    """cpk_packed_size_batch: d_out_off[n+1] gets exactly what encode_batch
+    would write there for the same arguments -- no packed byte is produced,
+    no output buffer taken; d_out_off[n] is the total.  max_seg_words = 0
+    synchronises `stream` once, as encode_batch does."""
+    n = d_seg_word_off.numel() - 1
+    rc = self._lib.cpk_packed_size_batch(self.handle, d_in.data_ptr(), d_seg_word_off.data_ptr(), n,
+                                         int(max_seg_words), d_out_off.data_ptr(), self._stream(stream))
+    _check(rc, "cpk_packed_size_batch")
+
+
+def _packed_size_messages(self, d_in, d_seg_word_off, d_msg_seg_off, max_seg_words: int, d_out_off,
+                          stream=None):
+    """cpk_packed_size_messages: d_out_off[nm + nseg + 1] as encode_messages
+    lays it out (per message the table piece, then its segments)."""
+    nseg = d_seg_word_off.numel() - 1
+    nm = d_msg_seg_off.numel() - 1
+    rc = self._lib.cpk_packed_size_messages(self.handle, d_in.data_ptr(), d_seg_word_off.data_ptr(), nseg,
+                                            d_msg_seg_off.data_ptr(), nm, int(max_seg_words),
+                                            d_out_off.data_ptr(), self._stream(stream))
+    _check(rc, "cpk_packed_size_messages")
+
+
+def _packed_size_host(self, data: np.ndarray, seg_word_off: np.ndarray) -> np.ndarray:
+    """cpk_packed_size_host -> out_off uint64[n+1]: the packed piece offsets
+    encode_host would return, without the packed bytes."""
+    swo = np.ascontiguousarray(seg_word_off, dtype=np.uint64)
+    n = len(swo) - 1
+    data = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    _check(self._lib.cpk_packed_size_host(self.handle, data.ctypes.data if data.size else None,
+                                          swo.ctypes.data, n, off.ctypes.data), "cpk_packed_size_host")
+    return off
+
+
+def _packed_size_messages_host(self, messages) -> np.ndarray:
+    """cpk_packed_size_messages_host for a list of messages (each a list of
+    segments, bytes of whole words) -> out_off uint64[messages + segments +
+    1] in message order (table, segments); the last entry is the length of
+    what SerializePacked.write would produce for all of them."""
+    segs = [bytes(s) for m in messages for s in m]
+    swo = np.concatenate([[0], np.cumsum([len(s) // 8 for s in segs], dtype=np.uint64)]).astype(np.uint64)
+    mso = np.concatenate([[0], np.cumsum([len(m) for m in messages], dtype=np.uint64)]).astype(np.uint64)
+    data = np.frombuffer(b"".join(segs) + b"\0" * 8, np.uint8)
+    off = np.zeros(len(messages) + len(segs) + 1, np.uint64)
+    _check(self._lib.cpk_packed_size_messages_host(self.handle, data.ctypes.data, swo.ctypes.data, len(segs),
+                                                   mso.ctypes.data, len(messages), off.ctypes.data),
+           "cpk_packed_size_messages_host")
+    return off
+
+
+Context.packed_size_batch = _packed_size_batch
+Context.packed_size_messages = _packed_size_messages
+Context.packed_size_host = _packed_size_host
+Context.packed_size_messages_host = _packed_size_messages_host
 
 
 def gen_params(cfg: int, z: float, lz: float, q: float) -> GenParams:

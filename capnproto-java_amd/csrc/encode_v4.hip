@@ -256,6 +256,9 @@ __device__ __forceinline__ uint32_t e4_next_piece(uint32_t *ticket, int &xq, int
 }
 
 // ---- pass 1: packed size of every piece --------------------------------------
+// kRows = false: the sizes alone, no boundary rows for an emit pass (the
+// size query, encode_size.hip); bvbuf / stride are then unused
+template <bool kRows = true>
 __global__ __launch_bounds__(kE4Threads, kE4Wpe) void e4_size_kernel(
     const uint64_t *__restrict__ in, const uint64_t *__restrict__ swo, uint32_t n,
     uint64_t *__restrict__ sizes, uint32_t *ticket, uint64_t hint, uint32_t *err,
@@ -356,7 +359,7 @@ __global__ __launch_bounds__(kE4Threads, kE4Wpe) void e4_size_kernel(
         st = e4g_state_after(G, cnt, st);
         // run boundaries for the emit pass (e4_classify's BV): past the
         // piece's end, every M word, each zero run / D/L stretch's first word
-        {
+        if (kRows) {
           const bool act = lane < cnt;
           const uint64_t Z = act ? ((uint64_t)G.zl | ((uint64_t)G.zh << 32)) : 0ull;
           const uint64_t DL = act ? ((uint64_t)G.dll | ((uint64_t)G.dlh << 32)) : 0ull;

@@ -318,6 +318,28 @@ struct SerializePacked {
     return off[n + 1];
   }
 
+  // The byte count SerializePacked.write would produce for the message,
+  // without producing it (the packed counterpart of
+  // Serialize.computeSerializedSizeInWords, Serialize.java:229): for a length
+  // prefix, or an exactly sized buffer.  The segments are concatenated for
+  // the one call (cpk_packed_size_messages_host), the table is built and
+  // sized on the device.
+  static size_t packedSize(Gpu &gpu, const std::vector<std::vector<uint8_t>> &segs) {
+    const size_t n = segs.size();
+    std::vector<uint64_t> swo = {0}, mso = {0, n}, off(n + 2);
+    std::vector<uint8_t> words;
+    for (size_t i = 0; i < n; ++i) {
+      if (segs[i].size() % 8) throw std::invalid_argument("segment not word-aligned");
+      words.insert(words.end(), segs[i].begin(), segs[i].end());
+      swo.push_back(swo.back() + segs[i].size() / 8);
+    }
+    words.resize(words.size() + 8);  // (a valid pointer for a message of empty segments)
+    check(cpk_packed_size_messages_host(gpu.get(), words.data(), swo.data(), (uint32_t)n, mso.data(), 1,
+                                        off.data()),
+          "SerializePacked.packedSize");
+    return off[n + 1];
+  }
+
   // SerializePacked.read into a reusable MessageView (its segments views of
   // one word buffer, as Serialize.read slices one ByteBuffer).
   static void read(Gpu &gpu, ArrayInputStream &in, MessageView &msg, uint64_t traversal_limit_words = 8ull << 20) {

@@ -43,6 +43,7 @@ struct cpk_ctx_s {
   uint64_t rm_mw_max;     // cpk_read_message[_host]: streams under it by one workgroup (<= kRmMwMax)
   int e4_order;           // cpk_encode_messages' two passes, segments largest first: 1 both passes,
                           // 2 the emit pass only, 0 neither (CPK_E4_ORDER)
+  int size_form;          // cpk_packed_size_batch: 0 by piece size, 1 chunk parallel, 2 wave per piece (CPK_SIZE_FORM)
   bool trace;
   double tr_us[8];
   uint64_t tr_n[8];
@@ -266,6 +267,9 @@ int cpk_ctx_create(int device, cpk_ctx *out) {
     c->rm_mw_max = m ? (uint64_t)atoll(m) << 10 : 0;
     const char *o = getenv("CPK_E4_ORDER");
     c->e4_order = o ? atoi(o) : 1;
+    // CPK_SIZE_FORM=chunk / wave forces the size query's form (A/B of its gate)
+    const char *z = getenv("CPK_SIZE_FORM");
+    c->size_form = (z && z[0] == 'c') ? 1 : (z && z[0] == 'w') ? 2 : 0;
   }
   if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
     c->cus = 256;
@@ -490,7 +494,7 @@ int e4_encode(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, 
                        d_swo, n);
   }
   const unsigned grid = e4_grid(ctx, n);
-  hipLaunchKernelGGL(cpk::e4_size_kernel, dim3(grid), dim3(cpk::kE4Threads), 0, s,
+  hipLaunchKernelGGL(cpk::e4_size_kernel<true>, dim3(grid), dim3(cpk::kE4Threads), 0, s,
                      (const uint64_t *)d_in, d_swo, n, sizes, ctx->tickets + cpk::kTkEnc, hint,
                      ctx->tickets + cpk::kTkErr, ctx->e4_bv.p, stride,
                      gate ? (const uint32_t *)(ctx->tickets + cpk::kTkGate + 2) : (const uint32_t *)nullptr,
@@ -561,7 +565,7 @@ int cpk_encode_messages_cap(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo
   }
   const uint32_t *size_order = ctx->e4_order == 1 ? order : nullptr;
   if (nseg)
-    hipLaunchKernelGGL(cpk::e4_size_kernel, dim3(grid), dim3(cpk::kE4Threads), 0, s,
+    hipLaunchKernelGGL(cpk::e4_size_kernel<true>, dim3(grid), dim3(cpk::kE4Threads), 0, s,
                        (const uint64_t *)d_in, d_swo, nseg, ssize, ctx->tickets + cpk::kTkEnc,
                        max_seg_words, ctx->tickets + cpk::kTkErr, ctx->e4_bv.p, stride, (const uint32_t *)nullptr,
                        size_order);
@@ -616,6 +620,122 @@ int cpk_encode_batch_cap(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, u
   if (rc) return rc;
   return sp_launch(ctx, d_in, d_swo, nullptr, nullptr, n, max_seg_words, d_out, d_out_off, s, true,
                    sp_unit_bound(n, max_seg_words), out_cap);
+}
+
+// ---- exact packed sizes without encoding (encode_size.hip) -----------------
+// The wave-per-piece size walk without boundary rows: sizes[i] = piece i's
+// packed bytes.  skip: the device gate's word (nonzero: the other form took
+// the batch); order: the pieces largest first, or null.
+static void size_walk_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, uint64_t hint,
+                             uint64_t *sizes, const uint32_t *skip, const uint32_t *order, hipStream_t s) {
+  hipLaunchKernelGGL(cpk::e4_size_kernel<false>, dim3(e4_grid(ctx, n)), dim3(cpk::kE4Threads), 0, s,
+                     (const uint64_t *)d_in, d_swo, n, sizes, ctx->tickets + cpk::kTkEnc, hint,
+                     ctx->tickets + cpk::kTkErr, (uint64_t *)nullptr, (uint64_t)0, skip, order);
+}
+
+int cpk_packed_size_batch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n,
+                          uint64_t max_seg_words, uint64_t *d_out_off, void *stream) {
+  if (!ctx || (!d_swo && n) || !d_out_off) return CPK_EINVAL;
+  if ((uintptr_t)d_in & 7) return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
+  // a bound on the batch's 8192-word units (0: every piece is one): from the
+  // hint, or from the batch's word count read back (synchronising the stream,
+  // as cpk_encode_batch without a hint).  The chunk-parallel form is enqueued
+  // (for the device to choose) when its unit table stays of bounded size.
+  uint64_t ub = sp_unit_bound(n, max_seg_words);
+  if (!max_seg_words) {
+    uint64_t ends[2];
+    int rc = read_words(ctx, s, {d_swo, d_swo + n}, ends);
+    if (rc) return rc;
+    const uint64_t total = ends[1] - ends[0];
+    ub = total > 64ull * cpk::kSpCS ? n + total / (64ull * cpk::kSpCS) + 1 : 0;
+  }
+  const bool can_chunk = ctx->size_form != 2 && ub <= (1ull << 25);
+  const uint32_t nb = scan_blocks(n);
+  int rc = reserve(ctx->status, (uint64_t)n + nb + 1, 1024);
+  if (rc) return rc;
+  uint64_t *sizes = ctx->status.p, *bsum = sizes + n;
+  uint32_t *mm = ctx->tickets + cpk::kTkGate;
+  if (hipMemsetAsync(ctx->tickets, 0, cpk::kTkErr * 4, s) != hipSuccess ||
+      hipMemsetAsync(sizes, 0, (uint64_t)n * 8, s) != hipSuccess || hipMemsetAsync(mm, 0xff, 4, s) != hipSuccess ||
+      hipMemsetAsync(mm + 1, 0, 4, s) != hipSuccess)
+    return CPK_EDEVICE;
+  // the form, decided on the device from the piece sizes (no host sync, no
+  // sample of the words)
+  const unsigned mg = n < 256u * 256u ? (unsigned)((n + 255) / 256) : 256u;
+  hipLaunchKernelGGL(cpk::e4_minmax_kernel, dim3(mg), dim3(256), 0, s, d_swo, n, mm, (const uint64_t *)nullptr);
+  hipLaunchKernelGGL(cpk::sz_gate_kernel, dim3(1), dim3(64), 0, s, ctx->tickets, d_swo, n, can_chunk ? 1u : 0u,
+                     (uint32_t)ctx->size_form);
+  if (can_chunk) {
+    const uint64_t ucap = ub ? ub : n;
+    // the units' run-state words, epoch-tagged as the single pass's (sp_launch)
+    bool fresh = false;
+    if ((rc = reserve(ctx->sp_status, 2 * ucap, 8192, nullptr, &fresh))) return rc;
+    if (++ctx->sp_epoch > 0xffffu) {
+      ctx->sp_epoch = 1;
+      fresh = true;
+    }
+    if (fresh && hipMemsetAsync(ctx->sp_status.p, 0, ctx->sp_status.cap * 8, s) != hipSuccess) return CPK_EDEVICE;
+    const uint64_t *utab = nullptr, *nunits = nullptr;
+    if (ub) {
+      // unit counts -> starts (e4 scan) -> unit table (sp_launch)
+      if ((rc = reserve(ctx->sp_units, (uint64_t)n + (n + 1) + nb + 1 + ub))) return rc;
+      uint64_t *ucnt = ctx->sp_units.p, *ustart = ucnt + n, *ubsum = ustart + (n + 1), *tab = ubsum + nb + 1;
+      const unsigned tb = 256, tg = (n + tb - 1) / tb;
+      hipLaunchKernelGGL(cpk::sp_units_count_kernel, dim3(tg), dim3(tb), 0, s, d_swo, (const uint64_t *)nullptr, n,
+                         max_seg_words, ucnt);
+      scan_launch(ucnt, n, ubsum, ustart, s);
+      hipLaunchKernelGGL(cpk::sp_units_fill_kernel, dim3(tg), dim3(tb), 0, s, (const uint64_t *)ustart, n, tab);
+      utab = tab;
+      nunits = ustart + n;
+    }
+    unsigned grid = (unsigned)(cpk::kSzWpe * ctx->cus);
+    if (grid > ucap) grid = (unsigned)ucap;
+    hipLaunchKernelGGL(cpk::sz_chunk_kernel, dim3(grid), dim3(cpk::kSpThreads), 0, s, (const uint64_t *)d_in, d_swo,
+                       n, (unsigned long long *)sizes, ctx->tickets + cpk::kTkPlan, utab, nunits,
+                       ctx->sp_status.p + ucap, ctx->sp_epoch, max_seg_words, ctx->tickets + cpk::kTkErr);
+  }
+  size_walk_launch(ctx, d_in, d_swo, n, max_seg_words, sizes, ctx->tickets + cpk::kTkGate + 2, nullptr, s);
+  scan_launch(sizes, n, bsum, d_out_off, s);
+  return hip_ok(hipGetLastError());
+}
+
+int cpk_packed_size_messages(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t nseg,
+                             const uint64_t *d_msg_seg_off, uint32_t nm, uint64_t max_seg_words,
+                             uint64_t *d_out_off, void *stream) {
+  if (!ctx || !d_out_off || (nm && !d_msg_seg_off) || (nseg && !d_swo)) return CPK_EINVAL;
+  if ((uintptr_t)d_in & 7) return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (nm == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
+  const uint64_t np = (uint64_t)nm + nseg;  // pieces: a table per message + the segments
+  if (np > 0xffffffffull) return CPK_EINVAL;
+  const uint32_t nb = scan_blocks(np);
+  // scratch: segment sizes | table sizes | message-order sizes | block sums |
+  // the segments largest first (u32) | their class counts (u32)
+  int rc = reserve(ctx->status, (uint64_t)nseg + nm + np + nb + 1 + nseg / 2 + 1 + cpk::kOrdClasses / 2, 1024);
+  if (rc) return rc;
+  uint64_t *ssize = ctx->status.p, *tsize = ssize + nseg, *comb = tsize + nm, *bsum = comb + np;
+  uint32_t *sord = reinterpret_cast<uint32_t *>(bsum + nb + 1), *shist = sord + nseg + (nseg & 1);
+  if (hipMemsetAsync(ctx->tickets, 0, cpk::kTkErr * 4, s) != hipSuccess) return CPK_EDEVICE;
+  const unsigned tb = 256, tg = (nm + tb - 1) / tb;
+  if (nseg) {
+    // (segments largest first, as cpk_encode_messages' size pass)
+    const uint32_t *order = nullptr;
+    if (ctx->e4_order == 1) {
+      ord_launch(nullptr, nseg, shist, sord, s, d_swo);
+      order = sord;
+    }
+    size_walk_launch(ctx, d_in, d_swo, nseg, max_seg_words, ssize, nullptr, order, s);
+  }
+  // the tables, built on the device as the encoder builds them, sized in place
+  hipLaunchKernelGGL(cpk::msg_table_size_kernel, dim3(tg), dim3(tb), 0, s, d_swo, d_msg_seg_off, nm, tsize);
+  hipLaunchKernelGGL(cpk::msg_interleave_kernel, dim3(tg), dim3(tb), 0, s, d_msg_seg_off, nm,
+                     (const uint64_t *)tsize, (const uint64_t *)ssize, comb);
+  scan_launch(comb, (uint32_t)np, bsum, d_out_off, s);
+  return hip_ok(hipGetLastError());
 }
 
 int cpk_ctx_take_error(cpk_ctx ctx, void *stream) {

@@ -741,6 +741,97 @@ int cpk_encode_messages_host_gather(cpk_ctx ctx, const void *const *h_segs, cons
       h_swo, nseg, h_msg_seg_off, nm, h_out, h_out_cap, h_out_off);
 }
 
+// The size queries from host memory: the encoders' chunks through the same
+// pipeline, with no output bytes -- a chunk's words go up (one large piece or
+// message in its sub-chunks), the size call runs, its offsets come back and
+// land at the running total.
+int cpk_packed_size_host(cpk_ctx ctx, const void *h_in, const uint64_t *h_swo, uint32_t n, uint64_t *h_out_off) {
+  if (!ctx || !h_swo || !h_out_off || (n && !h_in && h_swo[n] > h_swo[0])) return CPK_EINVAL;
+  if (n == 0) {
+    h_out_off[0] = 0;
+    return CPK_OK;
+  }
+  for (uint32_t i = 0; i < n; ++i)
+    if (h_swo[i + 1] < h_swo[i]) return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  const uint8_t *src = (const uint8_t *)h_in;
+  std::vector<HostChunk> cs = host_chunks(h_swo, nullptr, n, host_chunk_bytes());
+  for (HostChunk &c : cs) c.out_cap = 0;
+  uint64_t base = 0;
+  // meta: swo [nk + 1] | out_off [nk + 1]
+  return run_chunks(
+      ctx, cs, ChunkForm{true, false, 0, src, [](const HostChunk &c) -> uint64_t { return 2 * (c.i1 - c.i0 + 1ull); }},
+      [&](uint8_t *pin, const HostChunk &c) { par_copy(pin, src + c.in0, c.in_len); },
+      [&](HostSlot &s, const HostChunk &c) {
+        const uint32_t nk = c.i1 - c.i0;
+        for (uint32_t j = 0; j <= nk; ++j) s.pin_meta[j] = h_swo[c.i0 + j] - h_swo[c.i0];
+        return nk + 1ull;
+      },
+      [&](HostSlot &s, const HostChunk &c, hipStream_t sk) {
+        const uint32_t nk = c.i1 - c.i0;
+        uint64_t *doff = s.d_meta + nk + 1;
+        if (int rc = cpk_packed_size_batch(ctx, s.d_in, s.d_meta, nk, c.maxw ? c.maxw : 1, doff, sk)) return rc;
+        return hip_ok(hipMemcpyAsync(s.pin_meta + nk + 1, doff, (nk + 1) * 8ull, hipMemcpyDeviceToHost, sk));
+      },
+      [&](HostSlot &s, const HostChunk &c) {
+        const uint32_t nk = c.i1 - c.i0;
+        const uint64_t *coff = s.pin_meta + nk + 1;
+        for (uint32_t j = 0; j <= nk; ++j) h_out_off[c.i0 + j] = base + coff[j];
+        base += coff[nk];
+        return ChunkOut{CPK_OK, (uint8_t *)s.pin_out, 0};
+      });
+}
+
+int cpk_packed_size_messages_host(cpk_ctx ctx, const void *h_in, const uint64_t *h_swo, uint32_t nseg,
+                                  const uint64_t *h_msg_seg_off, uint32_t nm, uint64_t *h_out_off) {
+  if (!ctx || !h_swo || !h_msg_seg_off || !h_out_off) return CPK_EINVAL;
+  if (nseg && h_swo[nseg] > h_swo[0] && !h_in) return CPK_EINVAL;
+  if (h_msg_seg_off[0] != 0 || h_msg_seg_off[nm] != nseg) return CPK_EINVAL;
+  for (uint32_t m = 0; m < nm; ++m)
+    if (h_msg_seg_off[m + 1] < h_msg_seg_off[m]) return CPK_EINVAL;
+  for (uint32_t i = 0; i < nseg; ++i)
+    if (h_swo[i + 1] < h_swo[i]) return CPK_EINVAL;
+  if (nm == 0) {
+    h_out_off[0] = 0;
+    return CPK_OK;
+  }
+  DeviceGuard g(ctx->device);
+  const uint8_t *src = (const uint8_t *)h_in + 8 * h_swo[0];
+  std::vector<HostChunk> cs = enc_msg_chunks(h_swo, h_msg_seg_off, nm, host_chunk_bytes());
+  for (HostChunk &c : cs) c.out_cap = 0;
+  uint64_t base = 0;
+  // meta: swo [ns + 1] | msg_seg_off [nmk + 1] | out_off [nmk + ns + 1]
+  auto up_words = [](const HostChunk &c) -> uint64_t { return (c.s1 - c.s0 + 1) + (c.i1 - c.i0 + 1ull); };
+  return run_chunks(
+      ctx, cs,
+      ChunkForm{true, false, 0, src,
+                [](const HostChunk &c) -> uint64_t {
+                  const uint64_t ns = c.s1 - c.s0, nmk = c.i1 - c.i0;
+                  return (ns + 1) + (nmk + 1) + (nmk + ns + 1);
+                }},
+      [&](uint8_t *pin, const HostChunk &c) { par_copy(pin, src + c.in0, c.in_len); },
+      [&](HostSlot &s, const HostChunk &c) {
+        const uint32_t ns = (uint32_t)(c.s1 - c.s0), nmk = c.i1 - c.i0;
+        for (uint32_t j = 0; j <= ns; ++j) s.pin_meta[j] = h_swo[c.s0 + j] - h_swo[c.s0];
+        for (uint32_t j = 0; j <= nmk; ++j) s.pin_meta[ns + 1 + j] = h_msg_seg_off[c.i0 + j] - c.s0;
+        return up_words(c);
+      },
+      [&](HostSlot &s, const HostChunk &c, hipStream_t sk) {
+        const uint32_t ns = (uint32_t)(c.s1 - c.s0), nmk = c.i1 - c.i0;
+        uint64_t *dm = s.d_meta, *doff = dm + up_words(c);
+        if (int rc = cpk_packed_size_messages(ctx, s.d_in, dm, ns, dm + ns + 1, nmk, c.maxw, doff, sk)) return rc;
+        return hip_ok(hipMemcpyAsync(s.pin_meta + up_words(c), doff, ((uint64_t)nmk + ns + 1) * 8,
+                                     hipMemcpyDeviceToHost, sk));
+      },
+      [&](HostSlot &s, const HostChunk &c) {
+        const uint64_t np = (c.i1 - c.i0) + (c.s1 - c.s0);
+        const uint64_t *coff = s.pin_meta + up_words(c);
+        for (uint64_t j = 0; j <= np; ++j) h_out_off[c.i0 + c.s0 + j] = base + coff[j];
+        base += coff[np];
+        return ChunkOut{CPK_OK, (uint8_t *)s.pin_out, 0};
+      });
+}
+
 // Decode: chunks of whole messages by packed bytes.  A chunk's table pass
 // gives its words and segments; the chunk is then decoded straight into the
 // caller's arrays at the running totals.  When the caller's capacities are

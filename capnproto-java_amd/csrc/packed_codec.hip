@@ -1603,6 +1603,7 @@ __global__ void gather8_kernel(Gather8 g, uint32_t k, uint64_t *out) {
 #include "encode_v4.hip"
 #include "encode_sp.hip"
 #include "encode_sp3.hip"
+#include "encode_size.hip"
 #include "decode_v2.hip"
 #include "stream_split.hip"
 #include "encode_ms.hip"

@@ -168,6 +168,48 @@ int cpk_encode_messages_cap(cpk_ctx ctx, const void *d_in, const uint64_t *d_seg
  * themselves. */
 int cpk_ctx_take_error(cpk_ctx ctx, void *stream);
 
+/* Exact packed sizes without encoding: what cpk_encode_batch /
+ * cpk_encode_messages would write to d_out_off for the same arguments, with
+ * no packed byte produced and no output buffer taken -- to allocate exactly
+ * instead of cpk_batch_packed_capacity() (about 1.25 x the unpacked bytes), to
+ * write a length prefix ahead of the packed bytes, or to see whether packing
+ * pays.  (The unpacked half of the question is the reference's
+ * Serialize.computeSerializedSizeInWords, Serialize.java:229.)  Device
+ * traffic is the unpacked words, read once, plus the offset array.  The form
+ * is chosen on the device from the piece sizes: a workgroup per 8192-word
+ * chunk for a batch with a piece of over one chunk and at least 1/2048 of the
+ * batch's words (one piece far larger than the rest, or few large pieces), a
+ * wave per piece otherwise; CPK_ENCODER has no say.
+ *   cpk_packed_size_batch: d_out_off is uint64[n+1], device, written: [0] = 0,
+ *     [i+1] - [i] = piece i's packed bytes, [n] = the total.
+ *   cpk_packed_size_messages: d_out_off is uint64[nm + nseg + 1], laid out as
+ *     cpk_encode_messages lays it out: per message the table piece, then its
+ *     segments.  The tables are built and sized on the device as the encoder
+ *     builds them; none is stored to caller memory.
+ *   max_seg_words: as for cpk_encode_batch.  Nonzero: no host
+ *     synchronisation; a piece larger than the bound is reported by
+ *     cpk_ctx_take_error as CPK_EINVAL (its size is then undefined).  0 =
+ *     unknown: cpk_packed_size_batch reads d_seg_word_off[0], [n] back,
+ *     synchronising `stream`, as cpk_encode_batch does
+ *     (cpk_packed_size_messages needs no bound and takes 0 without a sync).
+ * Both are asynchronous on `stream` and never set CPK_ENOMEM in
+ * cpk_ctx_take_error.  n == 0 (nm == 0) is valid: d_out_off[0] = 0.  A piece
+ * of 0 words sizes to 0.  d_in is only read. */
+int cpk_packed_size_batch(cpk_ctx ctx, const void *d_in, const uint64_t *d_seg_word_off,
+                          uint32_t n, uint64_t max_seg_words, uint64_t *d_out_off, void *stream);
+int cpk_packed_size_messages(cpk_ctx ctx, const void *d_in, const uint64_t *d_seg_word_off,
+                             uint32_t nseg, const uint64_t *d_msg_seg_off, uint32_t nm,
+                             uint64_t max_seg_words, uint64_t *d_out_off, void *stream);
+/* The same from host memory; synchronous.  The words are staged through the
+ * context's pinned chunk pipeline as cpk_encode_host stages them (host to
+ * device only, in chunks of whole pieces or messages of CPK_HOST_CHUNK_MB, one
+ * large piece in its sub-chunks); only the offsets are copied back. */
+int cpk_packed_size_host(cpk_ctx ctx, const void *h_in, const uint64_t *h_seg_word_off,
+                         uint32_t n, uint64_t *h_out_off);
+int cpk_packed_size_messages_host(cpk_ctx ctx, const void *h_in, const uint64_t *h_seg_word_off,
+                                  uint32_t nseg, const uint64_t *h_msg_seg_off, uint32_t nm,
+                                  uint64_t *h_out_off);
+
 /* Batch decode of n pieces, device-resident (replaces n calls of
  * PackedInputStream.read, PackedInputStream.java:35-140).
  *   d_packed        : packed bytes, readable up to round_up(d_in_off[n], 16).
