@@ -1,22 +1,12 @@
 // encode_sp.hip -- single-pass encoder (the default).  Included from
-// packed_codec.hip (namespace cpk); uses encode_v4.hip's e4_tag.
+// packed_codec.hip (namespace cpk) after sp_chunk.hip.
 //
 // One 256-thread workgroup per chunk of a piece (a unit, below), units taken
 // in order from a ticket, the chunk held in VGPRs: wave w owns the 64-word
 // steps [32w, 32w + 32) of the 8192-word chunk, lane = word.  Per unit:
-//   A1  load the wave's steps (32 x 8 B per lane, all in flight); per word the
-//       nonzero-byte tag m (PackedOutputStream.java:64-117; kept packed four
-//       per VGPR); per step the Z / DL / D ballots (zero word, <= 1 zero
-//       byte, tag 0xff), stashed lane-per-step and copied to LDS for the
-//       other waves;
-//   A2  the roles PackedOutputStream.write gives each word, per step, from
-//       mask arithmetic and a carried state (scalar ALU): zero-run heads
-//       (:119-131), literal-run members (:133-193: a carry-add smears each
-//       0xFF head over the rest of its D/L stretch), 0xFF heads, run ends.
-//       Each wave recomputes the state entering its first step from the
-//       earlier steps' masks.  The packed bytes of the wave follow from
-//       popcounts.  tools/step_model.py is this algebra in Python, checked
-//       against the oracle (tests/test_step_model.py);
+//   A1, A2  the chunk algebra and the run state's hand-over, as sp_chunk.hip
+//       states them (A1's loads here: 32 x 8 B per lane, all in flight, the
+//       words kept for B; or in groups and read again by B, by form);
 //   look-back  the unit's size is published and its offset found by a
 //       decoupled look-back over the units before it (epoch-tagged 8-byte
 //       status words);
@@ -32,15 +22,17 @@
 // them is templated on the form (the ring and LDS layout, SpRegs, A1, B, the
 // kernel), everything else exists once.  The device gate picks the form
 // per batch (e4_gate_kernel, encode_v4.hip).
-
-#ifndef CPK_SP_WAVES
-#define CPK_SP_WAVES 4
-#endif
-constexpr int kSpWaves = CPK_SP_WAVES;
-constexpr int kSpThreads = 64 * kSpWaves;
-constexpr int kSpWS = 128 / kSpWaves;          // steps per wave
-constexpr int kSpCS = kSpWaves * kSpWS;        // steps per chunk (8192 words)
-static_assert(kSpWaves <= 16 && kSpWS >= 4 && kSpWS <= 32 && kSpWS % 4 == 0, "wave count");
+//
+// WRITTEN OUT HERE, on purpose: sp_a1 (both overloads), sp_lookahead_at and
+// sp_chunk below are this kernel's own text of what sp_chunk.hip holds once
+// for sp_small_kernel and sz_chunk_kernel (sp_a1_step / sp_a1_regs /
+// sp_a1_reload, sp_lookahead, SpGeom, SpHandover, sp_next_step, sp_a2,
+// sp_wave_bytes).  They use the shared SpStash, status words, sp_state_at,
+// sp_cont, sp_put_masks, sp_a2p / sp_a2_seq and sp_xs.  Joining this kernel
+// to any one of the shared pieces changes its register allocation, and with
+// all of them the dense form's encode measured 0.3 % slower
+// (docs/tuning_log.md): as written the three instantiations are the parent's
+// instructions.  A change to the protocol goes into SpHandover and here.
 
 // ---- the two forms ---------------------------------------------------------------
 // (the CPK_* macros: -D knobs for A/B builds of one form's value)
@@ -146,117 +138,10 @@ __device__ __forceinline__ uint32_t sp_rline(uint32_t i) {
   return (n & (n - 1)) == 0 ? (i & (n - 1)) : (i % n);
 }
 // scratch words: [0] ticket, [16..16 + waves) wave bytes, [5] piece offset,
-// [6..9] chunk exit state (two parities x {zl, dlo | hd << 1}), [11] the piece
-// (+ 1) whose offset [5] holds
-// Steps are scheduled one at a time: hoisting later steps' LUT reads and
-// lane reads ahead would keep them all live at once (VGPR spills).
-#define CPK_SP_STEP_FENCE() __builtin_amdgcn_sched_barrier(0)
+// [11] the piece (+ 1) whose offset [5] holds, [12] the state entering the chunk
 
-// status word per piece: [63:62] flag (1 aggregate, 2 inclusive prefix),
-// [61:46] launch epoch, [45:0] value (a relaxed 8-byte agent-scope granule:
-// the data is the flag, cdna_hip_programming.md Guideline 16 form R2)
-constexpr uint64_t kSpValMask = (1ull << 46) - 1;
-__device__ __forceinline__ uint64_t sp_word(uint32_t ep, uint32_t flag, uint64_t v) {
-  return ((uint64_t)flag << 62) | ((uint64_t)(ep & 0xffffu) << 46) | (v & kSpValMask);
-}
-__device__ __forceinline__ uint32_t sp_flag(uint64_t w, uint32_t ep) {
-  return (uint32_t)((w >> 46) & 0xffffu) == (ep & 0xffffu) ? (uint32_t)(w >> 62) : 0u;
-}
-
-// (SpSt and sp_roles: sp_roles.hip, included by encode_v4.hip)
-
-__device__ __forceinline__ uint64_t sp_ld(const uint64_t *p) { return sp_uni(*p); }
-
-// first D word at chunk position >= x and < lim, else lim
-__device__ int sp_first_d(const uint64_t *msk, int x, int lim) {
-  if (x >= lim) return lim;
-  int q = x >> 6;
-  uint64_t m = sp_ld(&msk[3 * q + 2]) & (~0ull << (x & 63));
-  while (!m) {
-    ++q;
-    if (q * 64 >= lim) return lim;
-    m = sp_ld(&msk[3 * q + 2]);
-  }
-  return min(q * 64 + __builtin_ctzll(m), lim);
-}
-
-// State entering chunk step s0 from the masks of the steps before it and
-// the chunk's entering state (tools/step_model.py: state_at); dep is set
-// when the result used the entering state (a zero run or D/L stretch over
-// every step before s0)
-__device__ SpSt sp_state_at(const uint64_t *msk, int s0, SpSt cst, bool &dep) {
-  if (s0 == 0) {
-    dep = true;
-    return cst;
-  }
-  SpSt st = {0u, 0u, 0u};
-  const uint64_t Zp = sp_ld(&msk[3 * (s0 - 1)]), DLp = sp_ld(&msk[3 * (s0 - 1) + 1]);
-  if (Zp >> 63) {
-    int q = s0 - 1;
-    uint32_t zl = 0;
-    uint64_t z = Zp;
-    while (z == ~0ull) {
-      zl += 64;
-      if (--q < 0) break;
-      z = sp_ld(&msk[3 * q]);
-    }
-    st.zl = zl + (q >= 0 ? (uint32_t)__builtin_clzll(~z) : cst.zl);
-    dep |= q < 0;
-  }
-  if (!(DLp >> 63)) return st;
-  st.dlo = 1;
-  int q = s0 - 1;
-  uint64_t d = DLp;
-  while (d == ~0ull) {
-    if (--q < 0) break;
-    d = sp_ld(&msk[3 * q + 1]);
-  }
-  const int P = 64 * s0;
-  int h;
-  if (q >= 0 || !cst.dlo || !cst.hd) {
-    const int start = q >= 0 ? 64 * q + 64 - __builtin_clzll(~d) : 0;
-    h = sp_first_d(msk, start, P);
-    if (h >= P) return st;
-  } else {
-    h = -(int)cst.hd;
-  }
-  dep |= q < 0;
-  for (;;) {
-    const int h2 = sp_first_d(msk, max(h + 256, 0), P);
-    if (h2 >= P) break;
-    h = h2;
-  }
-  st.hd = (uint32_t)min(P - h, 256);
-  return st;
-}
-
-// words of class cls (0: Z, 1: DL) from chunk step s on (<= 256); la: the
-// count continuing past the chunk's end
-__device__ uint32_t sp_cont(const uint64_t *msk, int s, int cs, int cls, uint32_t la) {
-  uint32_t r = 0;
-  for (int q = s; r < 256; ++q) {
-    if (q >= cs) {
-      r += la;
-      break;
-    }
-    const uint64_t m = sp_ld(&msk[3 * q + cls]);
-    if (m != ~0ull) {
-      r += (uint32_t)__builtin_ctzll(~m);
-      break;
-    }
-    r += 64;
-  }
-  return min(r, 256u);
-}
-
-// What a wave keeps of its steps from A1 to B, whatever the form
-struct SpStash {
-  uint32_t mp[kSpWS / 4];  // tags, four per register
-  uint32_t zl, zh, dll, dlh, dl_, dh_;                 // A1 stash: Z, DL, D (lane = step)
-  uint32_t oml, omh, ohl, ohh, oel, oeh;               // A2 stash: Mem, HC, E
-  uint32_t ox;                                         //   X: words past the step to the next run end
-};
-// ... and the words themselves, unless B reads them again (the words first: as they always lay)
+// What a wave keeps from A1 to B: SpStash (sp_chunk.hip), and the words
+// themselves unless B reads them again (the words first: as they always lay)
 struct SpWords {
   uint64_t v[kSpWS];  // step j in v[j]
 };
@@ -265,8 +150,9 @@ struct SpRegs : SpWords, SpStash {};
 template <class F>
 struct SpRegs<F, true> : SpStash {};
 
-// A1: the wave's cnt steps at src (wrem piece words from src on); returns
-// this lane's nonzero-byte count
+// A1 (written out, see the top; sp_chunk.hip: sp_a1_reload / sp_a1_regs): the
+// wave's cnt steps at src (wrem piece words from src on); returns this lane's
+// nonzero-byte count
 // kFull: the wave holds kSpWS whole steps -- straight-line code, so each
 // step waits only for its own load (vmcnt(kSpWS - 1 - j)); with the per-step
 // branches of the general form the compiler waits for all of them at the
@@ -353,145 +239,6 @@ __device__ __forceinline__ uint32_t sp_a1(SpRegs<F, false> &R, const uint64_t *_
     CPK_SP_STEP_FENCE();
   }
   return acc;
-}
-
-// the wave's masks to LDS (lane j = step sa + j)
-__device__ __forceinline__ void sp_put_masks(const SpStash &R, uint64_t *msk, int sa, int cnt, int lane) {
-  if (lane < cnt) {
-    uint64_t *m = msk + 3 * (sa + lane);
-    m[0] = (uint64_t)R.zl | ((uint64_t)R.zh << 32);
-    m[1] = (uint64_t)R.dll | ((uint64_t)R.dlh << 32);
-    m[2] = (uint64_t)R.dl_ | ((uint64_t)R.dh_ << 32);
-  }
-}
-
-// A2, sequential form (scalar ALU, one step at a time): the roles of the
-// wave's steps from the state entering its first step; stashes Mem
-// (literal-run members), HC (heads with a count byte) and E (run ends) at
-// lane = step (B needs no mask of the words without output: they are the
-// zero words that are no head); returns the steps' packed bytes beyond
-// their nonzero bytes.  nz0 / ndl0: bit 0 of the step after the wave's last.
-// Used when a D/L stretch longer than 192 words enters a step (a literal run
-// may end inside it); sp_a2p otherwise.
-__device__ __forceinline__ uint32_t sp_a2_seq(SpStash &R, int cnt, uint32_t wrem, SpSt st, uint32_t nz0, uint32_t ndl0) {
-  uint32_t bytes = 0;
-  for (int j = 0; j < cnt; ++j) {
-    const uint64_t Z = sp_rl(R.zl, R.zh, j), DL = sp_rl(R.dll, R.dlh, j), D = sp_rl(R.dl_, R.dh_, j);
-    const uint32_t vr = wrem - 64u * j;
-    const uint64_t V = vr >= 64 ? ~0ull : ((1ull << vr) - 1);
-    uint64_t Zh, Mem;
-    sp_roles(Z, DL, D, st, Zh, Mem);
-    const uint64_t HC = Zh | (D & ~Mem), ZO = (Z & ~Zh) | ~V;
-    bytes += (uint32_t)(__builtin_popcountll(~ZO & ~Mem) + __builtin_popcountll(Mem & ~D) +
-                        __builtin_popcountll(HC));
-    uint64_t z0 = nz0, d0 = ndl0;
-    if (j + 1 < cnt) {
-      z0 = (uint32_t)__builtin_amdgcn_readlane((int)R.zl, j + 1) & 1u;
-      d0 = (uint32_t)__builtin_amdgcn_readlane((int)R.dll, j + 1) & 1u;
-    }
-    const uint64_t E = (Z & ~((Z >> 1) | (z0 << 63))) | (DL & ~((DL >> 1) | (d0 << 63)));
-    R.oml = sp_wl(R.oml, (uint32_t)Mem, j);
-    R.omh = sp_wl(R.omh, (uint32_t)(Mem >> 32), j);
-    R.ohl = sp_wl(R.ohl, (uint32_t)HC, j);
-    R.ohh = sp_wl(R.ohh, (uint32_t)(HC >> 32), j);
-    R.oel = sp_wl(R.oel, (uint32_t)E, j);
-    R.oeh = sp_wl(R.oeh, (uint32_t)(E >> 32), j);
-  }
-  return bytes;
-}
-
-// value of v at lane src
-__device__ __forceinline__ uint32_t sp_from(uint32_t v, int src) {
-  return (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)v);
-}
-
-// A2, lane-parallel form: lane j computes step j's roles with 64-bit vector
-// ops; what carries from step to step (the zero run's length, whether the
-// D/L stretch entering a step already has its 0xFF head) comes from ballots
-// over the steps.  Exact while every literal run that enters a step covers
-// it to its end, i.e. no D/L stretch longer than 192 words enters a step:
-// returns false (nothing written) when one does.  Same stash as sp_a2_seq.
-__device__ __forceinline__ bool sp_a2p(SpStash &R, int cnt, uint32_t wrem, SpSt st, uint32_t nz0,
-                                       uint32_t ndl0, int lane, uint32_t &bytes) {
-  const bool act = lane < cnt;
-  const uint64_t Z = act ? ((uint64_t)R.zl | ((uint64_t)R.zh << 32)) : 0ull;
-  const uint64_t DL = act ? ((uint64_t)R.dll | ((uint64_t)R.dlh << 32)) : 0ull;
-  const uint64_t D = act ? ((uint64_t)R.dl_ | ((uint64_t)R.dh_ << 32)) : 0ull;
-  const uint64_t below = (1ull << lane) - 1;  // steps before this one
-  // ---- D/L stretch entering the step: its length (bounds the distance to
-  // its last head) and whether it has a head yet
-  const uint32_t dlo = (uint32_t)wave_shr1((int)(uint32_t)(DL >> 63), (int)st.dlo);
-  const uint32_t topdl = DL == ~0ull ? 64u : (uint32_t)__builtin_clzll(~DL);
-  const uint64_t notall = __ballot(!act || DL != ~0ull);
-  const uint64_t kdm = notall & below;
-  const int kd = kdm ? 63 - __builtin_clzll(kdm) : -1;  // last step before with a non-D/L word
-  const uint32_t topdl_k = sp_from(topdl, kd < 0 ? 0 : kd);
-  const uint32_t len = kd >= 0 ? topdl_k + 64u * (uint32_t)(lane - 1 - kd)
-                               : (st.dlo ? st.hd : 0u) + 64u * (uint32_t)lane;
-  const bool cont = act && dlo && (DL & 1);
-  if (__ballot(cont && len > 192)) return false;
-  const uint64_t anyD = __ballot(act && D != 0);
-  const bool topd = topdl > 0 && (D >> (64 - topdl)) != 0;
-  const uint64_t TD = __ballot(act && topd);
-  const uint64_t btw = anyD & below & (kd >= 0 ? (~0ull << kd) << 1 : ~0ull);
-  const bool head = btw != 0 || (kd >= 0 ? ((TD >> kd) & 1) != 0 : (st.dlo && st.hd));
-  const uint64_t cin = (cont && head) ? 1ull : 0ull;
-  const uint64_t A = ((D << 1) | cin) & DL;
-  const uint64_t C = (DL + A) ^ DL ^ A;
-  const uint64_t Mem = DL & (A | C);
-  // ---- zero runs: heads at run starts and every 256 words
-  const uint32_t zc = (uint32_t)wave_shr1((int)(uint32_t)(Z >> 63), st.zl ? 1 : 0);
-  uint64_t Zh = Z & ~((Z << 1) | zc);
-  {
-    const uint32_t topz = Z == ~0ull ? 64u : (uint32_t)__builtin_clzll(~Z);
-    const uint64_t kzm = __ballot(!act || Z != ~0ull) & below;
-    const int kz = kzm ? 63 - __builtin_clzll(kzm) : -1;
-    const uint32_t topz_k = sp_from(topz, kz < 0 ? 0 : kz);
-    const uint32_t zl = kz >= 0 ? topz_k + 64u * (uint32_t)(lane - 1 - kz) : st.zl + 64u * (uint32_t)lane;
-    const uint32_t j0 = (256u - (zl & 255u)) & 255u;
-    if (__ballot(act && zc && (Z & 1) && j0 < 64)) {
-      const uint64_t pre = j0 >= 63 ? ~0ull : ((2ull << j0) - 1);
-      if (act && zc && (Z & 1) && j0 < 64 && (Z & pre) == pre) Zh |= 1ull << j0;
-    }
-  }
-  // ---- per step: output masks, run ends, bytes
-  const uint32_t vr = act ? wrem - 64u * (uint32_t)lane : 0u;
-  const uint64_t V = vr >= 64 ? ~0ull : ((1ull << vr) - 1);
-  const uint64_t HC = Zh | (D & ~Mem), ZO = (Z & ~Zh) | ~V;
-  // bit 0 of the next step (lane + 1; the wave's last step: nz0 / ndl0)
-  uint32_t zn = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)Z, 0x130, 0xf, 0xf, false) & 1u;
-  uint32_t dn = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)DL, 0x130, 0xf, 0xf, false) & 1u;
-  if (lane == cnt - 1) {
-    zn = nz0;
-    dn = ndl0;
-  }
-  const uint64_t E = (Z & ~((Z >> 1) | ((uint64_t)zn << 63))) | (DL & ~((DL >> 1) | ((uint64_t)dn << 63)));
-  uint32_t b = act ? (uint32_t)(__builtin_popcountll(~ZO & ~Mem) + __builtin_popcountll(Mem & ~D) +
-                                __builtin_popcountll(HC))
-                   : 0u;
-  bytes = (uint32_t)__builtin_amdgcn_readlane(wave_incl_add((int)b), 63);
-  R.oml = (uint32_t)Mem;
-  R.omh = (uint32_t)(Mem >> 32);
-  R.ohl = (uint32_t)HC;
-  R.ohh = (uint32_t)(HC >> 32);
-  R.oel = (uint32_t)E;
-  R.oeh = (uint32_t)(E >> 32);
-  return true;
-}
-
-// X per step (lane = step): words past the step's end to the first run end
-// after it (a head's count reaches that far), from the next step with a run
-// end; past the wave's last step, Xlast.  At most 256.
-__device__ __forceinline__ void sp_xs(SpStash &R, int cnt, uint32_t Xlast, int lane) {
-  const bool act = lane < cnt;
-  const uint64_t E = (uint64_t)R.oel | ((uint64_t)R.oeh << 32);
-  const uint64_t en = __ballot(act && E != 0);
-  const uint64_t km = lane == 63 ? 0ull : (en & (~0ull << (lane + 1)));
-  const int k = km ? __builtin_ctzll(km) : 64;
-  const uint32_t ce = E ? (uint32_t)__builtin_ctzll(E) : 64u;
-  const uint32_t ce_k = sp_from(ce, k & 63);
-  uint32_t X = k < cnt ? 64u * (uint32_t)(k - lane - 1) + ce_k : 64u * (uint32_t)(cnt - 1 - lane) + Xlast;
-  R.ox = min(X, 256u);
 }
 
 // ---- the output ring -----------------------------------------------------------
@@ -726,9 +473,10 @@ __device__ __forceinline__ void sp_b(SpRegs<F> &R, int cnt, const uint64_t *lut,
   wave_lds_order();
 }
 
-// Look-ahead past a chunk: the zero run / D/L stretch continuing from the
-// chunk's end (<= 256 words each), from the next 4 steps' words.
-__device__ __forceinline__ void sp_lookahead(const uint64_t *__restrict__ src, uint32_t avail, int lane,
+// Look-ahead past a chunk (written out, see the top; sp_chunk.hip:
+// sp_lookahead): the zero run / D/L stretch continuing from the chunk's end
+// (<= 256 words each), from the next 4 steps' words.
+__device__ __forceinline__ void sp_lookahead_at(const uint64_t *__restrict__ src, uint32_t avail, int lane,
                                              uint32_t &laz, uint32_t &ladl) {
   uint32_t rz = 0, rd = 0;
   bool oz = true, od = true;
@@ -791,7 +539,7 @@ __device__ uint64_t sp_lookback(uint64_t *status, uint32_t p, uint64_t agg, uint
       if (lane == 0) atomicAdd(&g_phase[42], 1ull);  // polls that met an unpublished predecessor
 #endif
       if (++spins > (1u << 22)) {  // cannot happen: every predecessor is held by a running workgroup
-        if (lane == 0) atomicOr(err, 4u);
+        if (lane == 0) atomicOr(err, kErrWait);
         break;
       }
       __builtin_amdgcn_s_sleep(1);
@@ -816,17 +564,11 @@ __device__ uint64_t sp_lookback(uint64_t *status, uint32_t p, uint64_t agg, uint
 #define SP_A1_ARGS
 #define SP_A1_STAMP
 #endif
-// run state <-> a look-back value (zl < 2^31, dlo, hd <= 256: 41 bits)
-__device__ __forceinline__ uint64_t sp_pack_state(SpSt s) {
-  return (uint64_t)s.zl | ((uint64_t)s.dlo << 31) | ((uint64_t)s.hd << 32);
-}
-__device__ __forceinline__ SpSt sp_unpack_state(uint64_t v) {
-  SpSt s = {(uint32_t)v & 0x7fffffffu, (uint32_t)(v >> 31) & 1u, (uint32_t)(v >> 32) & 0x1ffu};
-  return s;
-}
 
-// One chunk's A1 + A2 for this wave (all waves call it; two barriers, three
-// when the chunk continues a piece).  Returns the chunk's packed bytes (all
+// One chunk's A1 + A2 for this wave (written out, see the top: the geometry
+// is sp_geom's without its guard, the hand-over SpHandover's, then sp_next_step, sp_a2,
+// sp_wave_bytes; all waves call it; two barriers, three when the chunk
+// continues a piece).  Returns the chunk's packed bytes (all
 // waves); wbefore: bytes of the waves before this one.  The state entering
 // the chunk is fresh (a piece's first chunk) or the run state the
 // predecessor chunk of the piece published (prev, epoch-tagged, flag 2),
@@ -882,7 +624,7 @@ __device__ __forceinline__ uint64_t sp_chunk(SpRegs<F> &R, const uint64_t *__res
       uint64_t v;
       while (sp_flag(v = ld_status(prev), ep) != 2u) {
         if (++spins > (1u << 24)) {  // cannot happen: see above
-          atomicOr(err, 4u);
+          atomicOr(err, kErrWait);
           break;
         }
         __builtin_amdgcn_s_sleep(1);
@@ -904,7 +646,7 @@ __device__ __forceinline__ uint64_t sp_chunk(SpRegs<F> &R, const uint64_t *__res
       // the step after the wave's last: in the chunk, or past it (look-ahead)
       uint32_t laz = 0, ladl = 0;
       const uint32_t wend = wfirst + 64u * cnt;
-      if (last && wend < W) sp_lookahead(pw + wend, W - wend, lane, laz, ladl);
+      if (last && wend < W) sp_lookahead_at(pw + wend, W - wend, lane, laz, ladl);
       if (sa + cnt < cs) {
         nz0 = (uint32_t)sp_ld(&msk[3 * (sa + cnt)]) & 1u;
         ndl0 = (uint32_t)sp_ld(&msk[3 * (sa + cnt) + 1]) & 1u;
@@ -1023,7 +765,7 @@ __global__ __launch_bounds__(kSpThreads, F::kWpe) void sp_encode_kernel(
     // (with a unit table, a piece over the hint is one empty unit: see
     // sp_units_count_kernel)
     bool bad = W64 >= (1ull << 31) || (!utab && W64 > 64ull * kSpCS) || (utab && hint && W64 > hint);
-    if ((bad || (hint && W64 > hint)) && threadIdx.x == 0 && c == 0) atomicOr(err, 1u);
+    if ((bad || (hint && W64 > hint)) && threadIdx.x == 0 && c == 0) atomicOr(err, kErrHint);
     const uint32_t W = bad ? 0u : (uint32_t)W64;  // (unsupported: sized 0, output undefined)
     const uint64_t *pw = base + w0;
     const uint32_t nch = max((((W + 63) >> 6) + kSpCS - 1) / kSpCS, 1u);

@@ -1,12 +1,10 @@
 // encode_sp3.hip -- one workgroup encoding a small batch in order: the
 // one-launch kernel behind the host path for small messages
 // (cpk_encode_messages_host / cpk_encode_host, host_pipe.hip).  Included from
-// packed_codec.hip after encode_sp.hip (namespace cpk); reuses the single
-// pass's per-unit algebra (A1 tags / ballots, A2 roles, B strings),
-// PackedOutputStream.java:35-205 restated per 8192-word chunk, with the
+// packed_codec.hip after encode_sp.hip (namespace cpk).  Per 8192-word chunk
+// it runs the chunk algebra and hand-over of sp_chunk.hip on words it loaded
+// into registers itself (V[]), then the single pass's B strings, with the
 // chunk's packed bytes staged whole in LDS and the output offset running.
-// Of encode_sp.hip it uses only what neither form of the single pass changes:
-// the chunk geometry, SpStash (its words live in V[]), the mask helpers and A2.
 //
 // (Round 4 also ran a pipelined batch encoder on these pieces -- each
 // workgroup with the next unit's words in flight and a whole-unit LDS stage,
@@ -21,190 +19,60 @@ constexpr uint32_t kSp3oStage = kSp3oScr + 32 * 8;
 constexpr uint32_t kSp3Lds = kSp3oStage + kSp3Stage;  // 79,136 B
 static_assert(kSp3oStage % 16 == 0, "LDS alignment");
 
-// One unit as a wave sees it: the piece, the chunk and this wave's steps.
-struct Sp3Unit {
-  const uint64_t *pw;  // the piece's first word
-  uint32_t W;          // piece words (0: an unsupported piece, sized 0)
-  uint32_t p, c;       // piece, chunk
-  bool lastc;          // the piece's last chunk
-  bool bad;            // unsupported (reported once)
-  bool over;           // more words than the caller's hint (reported once)
-  int cs;              // steps in the chunk
-  int sa, cnt;         // this wave's steps [sa, sa + cnt) of the chunk
-  uint32_t wfirst;     // the wave's first word (piece-relative)
-  uint32_t wrem;       // piece words from wfirst on (0: no steps)
-};
-
-// The wave's words of a chunk, every load issued (none waited for): step j
-// of lane l reads word min(64 j + l, last) -- a partial step or wave reads
-// its last word again, a wave without steps a valid dummy word.
-__device__ __forceinline__ void sp3_load(uint64_t (&V)[kSpWS], const Sp3Unit &u, const uint64_t *dummy, int lane) {
-  const uint64_t *src = u.cnt ? u.pw + u.wfirst : dummy;
-  const uint32_t last = u.cnt ? u.wrem - 1 : 0u;
+// The wave's words of a chunk (g) of the piece at pw, every load issued (none
+// waited for): step j of lane l reads word min(64 j + l, last) -- a partial
+// step or wave reads its last word again, a wave without steps a valid dummy
+// word.
+__device__ __forceinline__ void sp3_load(uint64_t (&V)[kSpWS], const uint64_t *pw, const SpGeom &g,
+                                         const uint64_t *dummy, int lane) {
+  const uint64_t *src = g.cnt ? pw + g.wfirst : dummy;
+  const uint32_t last = g.cnt ? g.wrem - 1 : 0u;
 #pragma unroll
   for (int j = 0; j < kSpWS; ++j) V[j] = ld_stream(src + min(64u * j + (uint32_t)lane, last));
 }
 
-// The four steps past the chunk (the zero run / D/L stretch continuing from
-// its end, for the last wave's head counts): issued with the unit's own
-// words, used only by the chunk's last wave when the piece continues.
-__device__ __forceinline__ bool sp3_la_need(const Sp3Unit &u) {
-  return u.cnt && u.sa + u.cnt == u.cs && u.wfirst + 64u * u.cnt < u.W;
-}
-__device__ __forceinline__ void sp3_la_load(uint64_t (&LA)[4], const Sp3Unit &u, const uint64_t *dummy, int lane) {
-  const bool need = sp3_la_need(u);
-  const uint32_t wend = u.wfirst + 64u * u.cnt;
-  const uint64_t *src = need ? u.pw + wend : dummy;
-  const uint32_t last = need ? u.W - wend - 1 : 0u;
+// The four steps past the chunk (sp_lookahead's words): issued with the
+// unit's own words, used only by the chunk's last wave when the piece (W
+// words) continues.
+__device__ __forceinline__ void sp3_la_load(uint64_t (&LA)[4], const uint64_t *pw, uint32_t W, const SpGeom &g,
+                                            const uint64_t *dummy, int lane) {
+  const bool need = g.last && g.wend() < W;
+  const uint64_t *src = need ? pw + g.wend() : dummy;
+  const uint32_t last = need ? W - g.wend() - 1 : 0u;
 #pragma unroll
   for (int j = 0; j < 4; ++j) LA[j] = ld_stream(src + min(64u * j + (uint32_t)lane, last));
 }
-__device__ __forceinline__ void sp3_lookahead(const uint64_t (&LA)[4], uint32_t avail, int lane, uint32_t &laz,
-                                              uint32_t &ladl) {
-  uint32_t rz = 0, rd = 0;
-  bool oz = true, od = true;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const bool valid = (uint32_t)lane < (avail > 64u * j ? avail - 64u * j : 0u);
-    const uint32_t m = valid ? e4_tag(LA[j]) : 0u;
-    const uint64_t Z = __ballot(valid && m == 0), DL = __ballot(__builtin_popcount(m) >= 7);
-    if (oz) {
-      if (Z == ~0ull) rz += 64;
-      else { rz += (uint32_t)__builtin_ctzll(~Z); oz = false; }
-    }
-    if (od) {
-      if (DL == ~0ull) rd += 64;
-      else { rd += (uint32_t)__builtin_ctzll(~DL); od = false; }
-    }
-  }
-  laz = rz;
-  ladl = rd;
-}
-
-// A1 on words already in registers: per word the nonzero-byte tag
-// (PackedOutputStream.java:64-117), per step the Z / DL / D ballots stashed
-// lane-per-step; returns this lane's nonzero bytes
-template <bool kFull>
-__device__ __forceinline__ uint32_t sp3_a1(SpStash &R, const uint64_t (&V)[kSpWS], uint32_t wrem, int cnt,
-                                           int lane) {
-  uint32_t acc = 0;
-#pragma unroll
-  for (int j = 0; j < kSpWS; ++j) {
-    if (kFull || j < cnt) {
-      const bool valid = kFull || (uint32_t)lane < wrem - 64u * j;
-      const uint32_t m = valid ? e4_tag(V[j]) : 0u;
-      if (j & 3) R.mp[j >> 2] |= m << (8 * (j & 3));
-      else R.mp[j >> 2] = m;
-      const uint32_t pc = (uint32_t)__builtin_popcount(m);
-      acc += pc;
-      const uint64_t Z = __ballot(valid && m == 0), DL = __ballot(pc >= 7), D = __ballot(m == 0xffu);
-      R.zl = sp_wl(R.zl, (uint32_t)Z, j);
-      R.zh = sp_wl(R.zh, (uint32_t)(Z >> 32), j);
-      R.dll = sp_wl(R.dll, (uint32_t)DL, j);
-      R.dlh = sp_wl(R.dlh, (uint32_t)(DL >> 32), j);
-      R.dl_ = sp_wl(R.dl_, (uint32_t)D, j);
-      R.dh_ = sp_wl(R.dh_, (uint32_t)(D >> 32), j);
-    }
-    CPK_SP_STEP_FENCE();
-  }
-  return acc;
-}
 
 // A of one unit (all waves; two barriers, three when the chunk continues a
-// piece): masks to LDS, the state entering the chunk (fresh, or what the
-// piece's previous chunk published: pst is a first probe of it, issued
-// with the loads), roles, the chunk's packed bytes (returned; wbefore /
-// wmine: bytes of the waves before this one / of this one).  The state the
-// chunk leaves goes to `next` when the piece continues.
+// piece; sp_chunk.hip) on words already in registers: V the wave's, LA the
+// look-ahead's, pst a first probe of h.prev, all issued together.  Returns
+// the chunk's packed bytes; wbefore: bytes of the waves before this one.
 __device__ __forceinline__ uint64_t sp3_chunk(SpStash &R, const uint64_t (&V)[kSpWS], const uint64_t (&LA)[4],
-                                              const Sp3Unit &u, uint64_t *msk, uint64_t *scr, uint64_t pst,
-                                              uint64_t *prev, uint64_t *next, uint32_t ep, uint32_t *err, int w,
-                                              int lane, uint32_t &Xlast, uint64_t &wbefore) {
-  const int cs = u.cs, sa = u.sa, cnt = u.cnt;
-  const uint32_t wrem = u.wrem, W = u.W;
+                                              uint32_t W, const SpGeom &g, uint64_t *msk, uint64_t *scr,
+                                              uint64_t pst, SpHandover h, int w, int lane, uint64_t &wbefore) {
   uint32_t acc = 0;
-  if (cnt) {
-    if (cnt == kSpWS && wrem >= 64u * kSpWS) acc = sp3_a1<true>(R, V, wrem, cnt, lane);
-    else acc = sp3_a1<false>(R, V, wrem, cnt, lane);
-    sp_put_masks(R, msk, sa, cnt, lane);
+  if (g.cnt) {
+    acc = g.full() ? sp_a1_regs<true>(R, V, g.wrem, g.cnt, lane) : sp_a1_regs<false>(R, V, g.wrem, g.cnt, lane);
+    sp_put_masks(R, msk, g.sa, g.cnt, lane);
   }
   __syncthreads();  // the chunk's masks in LDS
+  h.publish_early(msk, g, lane);
   SpSt cst = {0u, 0u, 0u};
-  // the state leaving the chunk depends on the entering one only when a zero
-  // run or D/L stretch covers the whole chunk: otherwise it is published now
-  bool early = false;
-  if (next && cnt && sa + cnt == cs) {
-    bool dep = false;
-    const SpSt ex = sp_state_at(msk, cs, cst, dep);
-    if (!dep) {
-      early = true;
-      if (lane == 0) st_status(next, sp_word(ep, 2u, sp_pack_state(ex)));
-    }
-  }
-  if (prev) {
-    if (threadIdx.x == 0) {
-      uint32_t spins = 0;
-      uint64_t v = pst;
-      while (sp_flag(v, ep) != 2u) {
-        if (++spins > (1u << 24)) {  // cannot happen: the predecessor chunk is held by a running workgroup
-          atomicOr(err, 4u);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        v = ld_status(prev);
-      }
-      scr[12] = v & kSpValMask;
-    }
-    __syncthreads();
-    cst = sp_unpack_state(sp_ld(&scr[12]));
-  }
-  SpSt st = cst;
+  if (h.prev) cst = h.wait<true>(pst, &scr[12]);
   uint32_t bytes = 0;
-  const bool last = cnt && sa + cnt == cs;  // this wave holds the chunk's last step
-  Xlast = 0;
-  if (cnt) {
+  if (g.cnt) {
     bool dep_ = false;
-    st = sp_state_at(msk, sa, cst, dep_);
-    uint32_t nz0 = 0, ndl0 = 0;
-    {
-      uint32_t laz = 0, ladl = 0;
-      const uint32_t wend = u.wfirst + 64u * cnt;
-      if (last && wend < W) sp3_lookahead(LA, W - wend, lane, laz, ladl);
-      if (sa + cnt < cs) {
-        nz0 = (uint32_t)sp_ld(&msk[3 * (sa + cnt)]) & 1u;
-        ndl0 = (uint32_t)sp_ld(&msk[3 * (sa + cnt) + 1]) & 1u;
-      } else {
-        nz0 = laz ? 1u : 0u;
-        ndl0 = ladl ? 1u : 0u;
-      }
-      const uint64_t Zl = sp_rl(R.zl, R.zh, cnt - 1), DLl = sp_rl(R.dll, R.dlh, cnt - 1);
-      const int cls = (Zl >> 63) ? 0 : ((DLl >> 63) ? 1 : -1);
-      if (cls >= 0) {
-        const uint32_t r = sp_cont(msk, sa + cnt, cs, cls, cls ? ladl : laz);
-        Xlast = r ? r - 1 : 0;
-      }
-    }
-    uint32_t rb = 0;
-    if (!sp_a2p(R, cnt, wrem, st, nz0, ndl0, lane, rb)) rb = sp_a2_seq(R, cnt, wrem, st, nz0, ndl0);
-    sp_xs(R, cnt, Xlast, lane);
+    const SpSt st = sp_state_at(msk, g.sa, cst, dep_);
+    uint32_t nz0, ndl0, Xlast;
+    auto la_word = [&](int j) __attribute__((always_inline)) { return LA[j]; };
+    sp_next_step(R, msk, g, W, lane, la_word, nz0, ndl0, Xlast);
+    const uint32_t rb = sp_a2(R, g.cnt, g.wrem, st, nz0, ndl0, lane);
+    sp_xs(R, g.cnt, Xlast, lane);
     bytes = rb + (uint32_t)__builtin_amdgcn_readlane(wave_incl_add((int)acc), 63);
   }
-  if (last && next && !early) {
-    bool dep_ = false;
-    st = sp_state_at(msk, cs, cst, dep_);
-    if (lane == 0) st_status(next, sp_word(ep, 2u, sp_pack_state(st)));
-  }
-  if (lane == 0) scr[16 + w] = bytes;
-  __syncthreads();  // wave bytes in LDS
-  uint64_t tot = 0;
-  wbefore = 0;
-#pragma unroll
-  for (int q = 0; q < kSpWaves; ++q) {
-    const uint64_t b = sp_ld(&scr[16 + q]);
-    if (q < w) wbefore += b;
-    tot += b;
-  }
-  return tot;
+  h.publish_late(msk, g, cst, lane);
+  uint64_t wmine;
+  return sp_wave_bytes(scr, bytes, w, lane, wbefore, wmine);
 }
 
 // B: the wave's strings OR-ed into the unit's LDS stage at unit-relative
@@ -362,26 +230,6 @@ constexpr uint32_t kSpSmallPieces = 512;   // piece descriptors staged in LDS (8
 constexpr uint32_t kSpSerialWords = 16;
 constexpr uint32_t kSpSmallLds = kSp3Lds + 16 * kSpSmallPieces + 8 * kSpSerialWords;
 
-__device__ __forceinline__ Sp3Unit sp3_unit_at(const uint64_t *pw, uint32_t W, uint32_t p, uint32_t c, int w) {
-  Sp3Unit u;
-  u.pw = pw;
-  u.W = W;
-  u.p = p;
-  u.c = c;
-  u.bad = u.over = false;
-  const uint32_t ns = (W + 63) >> 6;
-  const uint32_t nch = max((ns + kSpCS - 1) / kSpCS, 1u);
-  u.lastc = c + 1 >= nch;
-  const uint32_t cs0 = c * kSpCS;
-  u.cs = ns > cs0 ? (int)min((uint32_t)kSpCS, ns - cs0) : 0;
-  const int per = min(kSpWS, ((u.cs + kSpWaves - 1) / kSpWaves + 1) & ~1);
-  u.sa = w * per;
-  u.cnt = max(0, min(per, u.cs - u.sa));
-  u.wfirst = (cs0 + (uint32_t)u.sa) * 64;
-  u.wrem = u.cnt ? W - u.wfirst : 0;
-  return u;
-}
-
 // the descriptors of a batch of at most kSpArgPieces pieces, passed by value
 // (no dependent round trip to pinned memory before the first word loads)
 constexpr uint32_t kSpArgPieces = 8;
@@ -446,16 +294,16 @@ __global__ __launch_bounds__(kSpThreads, 1) void sp_small_kernel(const uint64_t 
       continue;
     }
     for (uint32_t c = 0; c < nch; ++c) {
-      const Sp3Unit u = sp3_unit_at(in + w0, W, p, c, w);
+      const SpGeom u = sp_geom(W, c, w);
       uint64_t V[kSpWS], LA[4];
-      sp3_load(V, u, desc, lane);
-      sp3_la_load(LA, u, desc, lane);
+      sp3_load(V, in + w0, u, desc, lane);
+      sp3_la_load(LA, in + w0, W, u, desc, lane);
+      // (the state passes through scr[24..25] by chunk parity, epoch 1)
       uint64_t *prev = c ? &scr[24 + ((c - 1) & 1)] : nullptr;
       uint64_t *next = u.lastc ? nullptr : &scr[24 + (c & 1)];
       const uint64_t pst = (prev && threadIdx.x == 0) ? ld_status(prev) : 0;
-      uint32_t Xlast = 0;
       uint64_t wbefore = 0;
-      const uint64_t ct = sp3_chunk(R, V, LA, u, msk, scr, pst, prev, next, 1u, lerr, w, lane, Xlast, wbefore);
+      const uint64_t ct = sp3_chunk(R, V, LA, W, u, msk, scr, pst, {prev, next, 1u, lerr}, w, lane, wbefore);
       if (u.cnt) sp3_b(R, V, u.cnt, lut, stage, (uint32_t)wbefore, lane);
       __syncthreads();
       sp3_flush(out, stage, g, ct, ocap);
@@ -467,7 +315,7 @@ __global__ __launch_bounds__(kSpThreads, 1) void sp_small_kernel(const uint64_t 
   __syncthreads();
   if (threadIdx.x == 0) {
     const bool bad = *reinterpret_cast<volatile uint32_t *>(lerr) != 0;
-    if (bad) atomicOr(err, 4u);
+    if (bad) atomicOr(err, kErrWait);
     out_off[n] = bad ? ~0ull : g;
   }
   if (flag) small_done(flag, seq);

@@ -273,7 +273,7 @@ __global__ __launch_bounds__(kE4Threads, kE4Wpe) void e4_size_kernel(
     const uint32_t seg = order ? (uint32_t)__builtin_amdgcn_readfirstlane((int)order[tk]) : tk;
     const uint64_t w0 = swo[seg];
     const uint64_t W = swo[seg + 1] - w0;
-    if (((hint && W > hint) || W >= (1ull << 31)) && lane == 0) atomicOr(err, 1u);
+    if (((hint && W > hint) || W >= (1ull << 31)) && lane == 0) atomicOr(err, kErrHint);
     if (W == 0) {  // an empty piece: no bytes (and no loads: it may sit at the end)
       if (lane == 0) sizes[seg] = 0;
       continue;

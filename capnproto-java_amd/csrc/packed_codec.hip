@@ -1601,6 +1601,7 @@ __global__ void gather8_kernel(Gather8 g, uint32_t k, uint64_t *out) {
 }
 
 #include "encode_v4.hip"
+#include "sp_chunk.hip"
 #include "encode_sp.hip"
 #include "encode_sp3.hip"
 #include "encode_size.hip"

@@ -3,7 +3,7 @@
 // and the run state entering it (SpSt, sp_roles), and the lane helpers the
 // single pass uses with them (readfirstlane / readlane / writelane pairs,
 // v_ffbl, per-lane selects on an SGPR mask).  Included once, by
-// encode_v4.hip (in namespace cpk), ahead of encode_sp.hip and
+// encode_v4.hip (in namespace cpk), ahead of sp_chunk.hip, encode_sp.hip and
 // encode_sp3.hip, which use it too.
 
 struct SpSt {

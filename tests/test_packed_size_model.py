@@ -14,7 +14,6 @@ from _packed_size_cases import boundary_pieces, PIECE_WORDS
 
 M64 = sm.M64
 WS, NW = 32, 4  # kSpWS, kSpWaves: 128 steps = 8192 words per chunk
-FRESH = (0, False, 0)
 
 
 def _masks(data):
@@ -33,30 +32,19 @@ def _masks(data):
     return list(zip(V, Z, DL, D)), int(nzb.sum())
 
 
-def _leaving_state_depends(masks):
-    """sp_state_at's `dep` for the state after the chunk's last step, from a
-    fresh entering state: a zero run over every step, or a D/L stretch over
-    every step that holds a 0xFF word."""
-    if (masks[-1][1] >> 63) & 1 and all(m[1] == M64 for m in masks):
-        return True
-    return bool((masks[-1][2] >> 63) & 1 and all(m[2] == M64 for m in masks) and any(m[3] for m in masks))
-
-
 def size_model(data):
     """-> (packed size, chunks whose leaving state was published early,
     chunks that published after taking their entering state)."""
     masks_all, nonzero_bytes = _masks(data)
     CS = WS * NW
     size, early, late = nonzero_bytes, 0, 0
-    handed = FRESH  # what the predecessor unit's status word holds
+    handed = sm.FRESH  # what the predecessor unit's status word holds
     for c0 in range(0, len(masks_all), CS):
         masks = masks_all[c0:c0 + CS]
         last_chunk = c0 + CS >= len(masks_all)
-        published = None
-        if not last_chunk and not _leaving_state_depends(masks):
-            published = sm.state_at(masks, len(masks), FRESH)  # before the wait
-            early += 1
-        cst = handed if c0 else FRESH
+        cst, handed, was_early = sm.handover(masks, handed, c0 == 0, last_chunk)
+        early += was_early
+        late += not last_chunk and not was_early
         for wv in range(NW):
             a, b = wv * WS, min((wv + 1) * WS, len(masks))
             if a >= b:
@@ -67,10 +55,6 @@ def size_model(data):
                 HC, ZO = Zh | (D & ~Mem), (Z & ~Zh) | (~V & M64)
                 # tags and literal-run members' zero bytes, counts
                 size += bin(~ZO & ~Mem & M64).count("1") + bin(Mem & ~D).count("1") + bin(HC).count("1")
-        if not last_chunk and published is None:
-            published = sm.state_at(masks, len(masks), cst)
-            late += 1
-        handed = published
     return size, early, late
 
 

@@ -1,4 +1,4 @@
-"""CPU model of the single-pass encoder's mask algebra (csrc/encode_sp.hip).
+"""CPU model of the single-pass encoder's mask algebra (csrc/sp_chunk.hip).
 
 The kernel never walks a piece word by word: it classifies 64-word steps
 into 64-bit masks (Z: zero word, DL: <= 1 zero byte, D: tag 0xff) and derives
@@ -168,6 +168,36 @@ def state_at(masks, s0, cst):
             break
         h = h2
     return (zl, True, min(P - h, 256))
+
+
+FRESH = (0, False, 0)  # the state entering a piece
+
+
+def leaving_state_depends(masks):
+    """sp_state_at's `dep` for the state after the chunk's last step, from a
+    fresh entering state: a zero run over every step, or a D/L stretch over
+    every step that holds a 0xFF word."""
+    if (masks[-1][1] >> 63) & 1 and all(m[1] == M64 for m in masks):
+        return True
+    return bool((masks[-1][2] >> 63) & 1 and all(m[2] == M64 for m in masks) and any(m[3] for m in masks))
+
+
+def handover(masks, handed, first_chunk, last_chunk):
+    """One chunk's part in handing the run state along a piece, in the
+    kernels' order (csrc/sp_chunk.hip, SpHandover): the leaving state is
+    published early, from a fresh entering state, when the chunk's masks
+    alone decide it; then the entering state is taken (`handed`: what the
+    predecessor published); a leaving state that needs it is published late.
+    -> (entering state, published state or None for a piece's last chunk,
+    whether it was published early)."""
+    published = None
+    early = not last_chunk and not leaving_state_depends(masks)
+    if early:
+        published = state_at(masks, len(masks), FRESH)  # before the wait
+    cst = FRESH if first_chunk else handed
+    if not last_chunk and not early:
+        published = state_at(masks, len(masks), cst)
+    return cst, published, early
 
 
 def encode_model(data, WS=32, NW=4):
