@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kSpThreads, kSzWpe) void sz_chunk_kernel(
 }
 
 // Which form sizes the batch, from the min / max piece words
-// (e4_minmax_kernel without its sample: tickets[kTkGate], [kTkGate + 1]):
+// (e4_minmax_kernel without its sample: tickets[kTkGate + kGateMin], [kTkGate + kGateMax]):
 // the chunk-parallel form for batches with a piece of over one 8192-word unit
 // and at least 1/2048 of the batch's words (a wave would walk it alone long
 // after the rest is done: the encode gate's rule for one dominant piece,
@@ -98,17 +98,17 @@ __global__ __launch_bounds__(kSpThreads, kSzWpe) void sz_chunk_kernel(
 // the walk's 11.39 / 11.00 / 11.19 -- its barriers and ordered ticket buy
 // nothing when every wave has a piece of its own.
 // The form not picked returns at once: the wave walk reads
-// tickets[kTkGate + 2], the chunk form finds its ordered ticket exhausted.
+// tickets[kTkGate + kGatePick], the chunk form finds its ordered ticket exhausted.
 // can_chunk: the chunk form was enqueued at all; force: 1 chunk form, 2 wave
 // per piece (CPK_SIZE_FORM).
 __global__ void sz_gate_kernel(uint32_t *tickets, const uint64_t *swo, uint32_t n, uint32_t can_chunk,
                                uint32_t force) {
-  const uint32_t hi = tickets[kTkGate + 1];
+  const uint32_t hi = tickets[kTkGate + kGateMax];
   const uint64_t total = swo[n] - swo[0];
   const bool big = hi > 8192u && (uint64_t)hi * 2048u >= total;
   const bool chunk = can_chunk && (force ? force == 1u : big);
   if (threadIdx.x == 0) {
-    tickets[kTkGate + 2] = chunk ? 1u : 0u;
+    tickets[kTkGate + kGatePick] = chunk ? 1u : 0u;
     tickets[kTkPlan] = chunk ? 0u : 0x7fffffffu;
   }
 }

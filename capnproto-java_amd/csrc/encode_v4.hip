@@ -640,12 +640,13 @@ __global__ __launch_bounds__(kE4Threads, kE4Wpe) void e4_emit_kernel(
 }
 
 // ---- encoder choice on the device (cpk_encode_batch, no host sync) --------
-// min / max piece words of the batch (mm[0] preset to ~0, mm[1] to 0)
+// min / max piece words of the batch (mm: the gate block, tickets + kTkGate;
+// mm[kGateMin] preset to ~0, mm[kGateMax] to 0)
 __global__ __launch_bounds__(256) void e4_minmax_kernel(const uint64_t *__restrict__ swo, uint32_t n,
                                                         uint32_t *mm, const uint64_t *__restrict__ in) {
   // (and one word per thread, one in each of G equal stretches of the
   // batch at a hashed position inside it -- not at a fixed phase, which
-  // would alias with the pieces' starts: zero words counted into mm[3] for
+  // would alias with the pieces' starts: zero words counted into mm[kGateZero] for
   // the single pass's sparse form, e4_gate_kernel)
   {
     const uint64_t a = swo[0], T = swo[n] - a;
@@ -654,10 +655,10 @@ __global__ __launch_bounds__(256) void e4_minmax_kernel(const uint64_t *__restri
     const uint64_t x = (in && T) ? in[a + g * T / G + (st ? h % st : 0)] : 1ull;
     const bool z = in && T && x == 0;
     const uint64_t zb = __ballot(z);
-    if ((threadIdx.x & 63) == 0 && zb) atomicAdd(&mm[3], (uint32_t)__builtin_popcountll(zb));
-    // (and the sampled words' packed bytes, tag + nonzero bytes, into mm[7])
+    if ((threadIdx.x & 63) == 0 && zb) atomicAdd(&mm[kGateZero], (uint32_t)__builtin_popcountll(zb));
+    // (and the sampled words' packed bytes, tag + nonzero bytes, into mm[kGateBytes])
     const int pb = wave_incl_add((in && T && x) ? 1 + __builtin_popcount(e4_tag(x)) : 0);
-    if ((threadIdx.x & 63) == 63 && pb) atomicAdd(&mm[7], (uint32_t)pb);
+    if ((threadIdx.x & 63) == 63 && pb) atomicAdd(&mm[kGateBytes], (uint32_t)pb);
   }
   // grid-stride over the pieces, one atomic pair per workgroup (one per
   // wave put 8 K same-address atomics in line at 1 Mi pieces: 97 us)
@@ -683,18 +684,18 @@ __global__ __launch_bounds__(256) void e4_minmax_kernel(const uint64_t *__restri
       lo = min(lo, red[0][k]);
       hi = max(hi, red[1][k]);
     }
-    atomicMin(&mm[0], lo);
-    atomicMax(&mm[1], hi);
+    atomicMin(&mm[kGateMin], lo);
+    atomicMax(&mm[kGateMax], hi);
   }
 }
 // like-sized pieces (the largest at most twice the smallest) of 4096 words
 // or more: the single pass (measured crossover, 1 GiB batches, config 2 / 3:
 // 2 Ki-word pieces 1.07 / 1.22 ms against the two passes' 0.87 / 0.89, 4 Ki
 // words 0.69 / 0.82 against 0.85 / 0.87) (its ticket left at 0, the two-pass kernels told
-// to skip, tickets[kTkGate + 2]); else the reverse (the single pass's
+// to skip, tickets[kTkGate + kGatePick]); else the reverse (the single pass's
 // ordered ticket exhausted)
 // Among single-pass batches, those whose sampled words are at least 85 %
-// zero take its sparse form (SpSparse: tickets[kTkGate + 6] = 1; config 4
+// zero take its sparse form (SpSparse: tickets[kTkGate + kGateSparse] = 1; config 4
 // encode -7 %, config 2 +36 %).
 // Dense batches (the sampled words' tags and nonzero bytes at least
 // CPK_GATE_DENSE_PCT % of their bytes) take the two passes instead: there a
@@ -718,17 +719,18 @@ __global__ __launch_bounds__(256) void e4_minmax_kernel(const uint64_t *__restri
 // rate.)
 __global__ void e4_gate_kernel(uint32_t *tickets, uint32_t samples, uint32_t force, const uint64_t *swo,
                                uint32_t n) {
-  const uint32_t lo = tickets[kTkGate], hi = tickets[kTkGate + 1];
+  const uint32_t lo = tickets[kTkGate + kGateMin], hi = tickets[kTkGate + kGateMax];
   const uint64_t total = swo[n] - swo[0];
   const bool big = hi > 8192u && (uint64_t)hi * 2048u >= total;
   const bool like = (lo >= 4096u && 2u * lo >= hi) || big;
-  const bool sparse = like && (force ? force == 2u : (uint64_t)tickets[kTkGate + 3] * 100u >= (uint64_t)samples * 85u);
+  const bool sparse =
+      like && (force ? force == 2u : (uint64_t)tickets[kTkGate + kGateZero] * 100u >= (uint64_t)samples * 85u);
   const bool dense = like && !big && !sparse && !force &&
-                     (uint64_t)tickets[kTkGate + 7] * 100u >= (uint64_t)samples * 8u * CPK_GATE_DENSE_PCT;
+                     (uint64_t)tickets[kTkGate + kGateBytes] * 100u >= (uint64_t)samples * 8u * CPK_GATE_DENSE_PCT;
   const bool sp = like && !dense;
   if (threadIdx.x == 0) {
-    tickets[kTkGate + 6] = sparse ? 1u : 0u;
-    tickets[kTkGate + 2] = sp ? 1u : 0u;
+    tickets[kTkGate + kGateSparse] = sparse ? 1u : 0u;
+    tickets[kTkGate + kGatePick] = sp ? 1u : 0u;
     tickets[kTkPlan] = sp ? 0u : 0x7fffffffu;
   }
 }

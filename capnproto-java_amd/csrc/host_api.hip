@@ -1,8 +1,8 @@
 // host_api.hip -- the host layer: the context and its scratch buffers, the
 // launch helpers and the C ABI (include/capnp_packed.h).  Included last by
 // packed_codec.hip, after every kernel: one translation unit.
+#include "carve.hip"  // Carve: a scratch layout written once (counted, then carved)
 
-// ================================================================ C ABI
 struct HostPipe;  // host_pipe.hip: staging of the host-memory forms
 
 // A device buffer of the context, allocated on first use (valid when zeroed:
@@ -37,13 +37,13 @@ struct cpk_ctx_s {
   uint64_t small_fallbacks;  // small_wait calls whose flag was unset even after a stream sync (lost flags)
   uint64_t small_timeouts;   // small_wait calls that waited past 5 ms (late launches included)
   DevBuf sp_units;        // single pass, pieces over one chunk: unit counts | starts | block sums | unit table
-  // CPK_HOST_TRACE=1 (read at creation): host wall time of the one-message
-  // host paths (cpk_encode_host[_gather], cpk_read_message_host) by phase,
-  // summed per context and printed to stderr by cpk_ctx_destroy
   uint64_t rm_mw_max;     // cpk_read_message[_host]: streams under it by one workgroup (<= kRmMwMax)
   int e4_order;           // cpk_encode_messages' two passes, segments largest first: 1 both passes,
                           // 2 the emit pass only, 0 neither (CPK_E4_ORDER)
   int size_form;          // cpk_packed_size_batch: 0 by piece size, 1 chunk parallel, 2 wave per piece (CPK_SIZE_FORM)
+  // CPK_HOST_TRACE=1 (read at creation): host wall time of the one-message
+  // host paths (cpk_encode_host[_gather], cpk_read_message_host) by phase,
+  // summed per context and printed to stderr by cpk_ctx_destroy
   bool trace;
   double tr_us[8];
   uint64_t tr_n[8];
@@ -109,6 +109,12 @@ hipError_t dec_tickets_reset(cpk_ctx ctx, hipStream_t s) {
   return hipMemsetAsync(ctx->tickets + cpk::kTkDec, 0, 8 * cpk::kTkStride * 4, s);
 }
 
+// every ticket counter and the plan ticket (the words below the error word)
+// back to zero: before the two passes and the size calls
+hipError_t enc_tickets_reset(cpk_ctx ctx, hipStream_t s) {
+  return hipMemsetAsync(ctx->tickets, 0, cpk::kTkErr * 4, s);
+}
+
 // the two passes' grid: persistent blocks of kE4Waves waves, a wave per piece
 unsigned e4_grid(cpk_ctx ctx, uint32_t n) {
   const unsigned grid = (unsigned)(8 * ctx->cus), want = (n + cpk::kE4Waves - 1) / cpk::kE4Waves;
@@ -158,6 +164,27 @@ int reserve_fixed(DevBuf &b, uint64_t bytes) {
   if (b.p || hipMalloc(&b.p, bytes) == hipSuccess) return CPK_OK;
   b.p = nullptr;
   return CPK_ENOMEM;
+}
+// Room in b for a layout, then its pointers: `layout(Carve &)` is the list of
+// take() calls, run once counting and once over the buffer.  fixed: one of
+// the fixed-size buffers (reserve_fixed), its layout the same for every call.
+template <class Layout>
+int carve_reserve(DevBuf &b, uint64_t floor, Layout layout, bool fixed = false) {
+  Carve count;
+  layout(count);
+  if (int rc = fixed ? reserve_fixed(b, count.n * 8) : reserve(b, count.n, floor)) return rc;
+  Carve c(b.p);
+  layout(c);
+  return CPK_OK;
+}
+
+// sizes [n] | the scan's block sums: the scratch of a size pass and its scan
+// (e4_encode, cpk_packed_size_batch)
+int sizes_scratch(cpk_ctx ctx, uint32_t n, uint64_t *&sizes, uint64_t *&bsum) {
+  return carve_reserve(ctx->status, 1024, [&](Carve &c) {
+    sizes = c.take(n);
+    bsum = c.take(scan_blocks(n) + 1);
+  });
 }
 }  // namespace
 
@@ -370,7 +397,25 @@ static int read_words(cpk_ctx ctx, hipStream_t s, std::initializer_list<const ui
 // small kernels and the e4 scan, no host sync: the unit count stays on the
 // device).  sp_takes screens which batches it takes; cpk_encode_batch lets
 // the device choose by the piece sizes (e4_gate_kernel).
-static uint64_t sp_unit_bound(uint64_t n, uint64_t hint);
+
+// A bound on the units of n pieces (0: every piece is one unit): from the
+// hint, no piece being over it; with no hint from the batch's word total,
+// which bounds every piece.  Over 2^32 units: unsupported.
+static uint64_t sp_unit_bound(uint64_t n, uint64_t hint, uint64_t total = 0) {
+  constexpr uint64_t chunk = 64ull * cpk::kSpCS;
+  if (hint) return hint <= chunk ? 0 : n * ((hint + chunk - 1) / chunk);
+  return total <= chunk ? 0 : n + total / chunk + 1;
+}
+// ... of a batch on the device: with no hint its word total is read back,
+// synchronising the stream
+static int sp_batch_unit_bound(cpk_ctx ctx, const uint64_t *d_swo, uint32_t n, uint64_t hint, hipStream_t s,
+                               uint64_t &ub) {
+  uint64_t ends[2] = {0, 0};
+  if (!hint)
+    if (int rc = read_words(ctx, s, {d_swo, d_swo + n}, ends)) return rc;
+  ub = sp_unit_bound(n, hint, ends[1] - ends[0]);
+  return CPK_OK;
+}
 // whether the single pass is enqueued at all (for the device to choose): a
 // size hint, and a unit table of bounded size for pieces over one chunk (a
 // loose hint would otherwise size it for nothing)
@@ -379,70 +424,81 @@ static bool sp_takes(cpk_ctx ctx, uint32_t n, uint64_t max_seg_words) {
   return ctx->encoder != 4 && max_seg_words != 0 && sp_unit_bound(n, max_seg_words) <= (1ull << 25);
 }
 
-// `units`: a bound on the batch's units when its pieces may exceed one
-// chunk (0: every piece is one unit)
-int sp_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, const uint64_t *pdesc,
-              const uint64_t *tin, uint32_t n, uint64_t hint, void *d_out, uint64_t *d_out_off,
-              hipStream_t s, bool gated = false, uint64_t units = 0, uint64_t out_cap = ~0ull) {
-  const uint64_t ucap = units ? units : n;  // look-back words (+ as many run-state words)
+// What a launch ticketed by units needs (sp_encode_kernel, sz_chunk_kernel;
+// both see the same epoch tagging, which SpHandover's no-hang argument
+// assumes): ucap look-back words and as many run-state words, tagged with a
+// new epoch, and the unit table when pieces may exceed one chunk.
+struct SpPlan {
+  uint64_t ucap;                  // units at most
+  uint64_t *status, *ustate;      // look-back words [ucap] | run-state words [ucap]
+  uint32_t epoch;                 // 1..65535
+  const uint64_t *utab, *nunits;  // the unit table and its count on the device; null: every piece one unit
+};
+// `units`: a bound on the batch's units when its pieces may exceed one chunk
+// (0: every piece is one unit).  pdesc, hint: as the kernels take them.
+static int sp_plan(cpk_ctx ctx, const uint64_t *d_swo, const uint64_t *pdesc, uint32_t n, uint64_t hint,
+                   uint64_t units, hipStream_t s, SpPlan &P) {
+  P.ucap = units ? units : n;
   // (a grown array's words are undefined, and a look-back polls them:
   // cleared below, as when the epoch wraps)
   bool fresh = false;
-  if (int rc = reserve(ctx->sp_status, 2 * ucap, 8192, nullptr, &fresh)) return rc;
+  if (int rc = reserve(ctx->sp_status, 2 * P.ucap, 8192, nullptr, &fresh)) return rc;
   if (++ctx->sp_epoch > 0xffffu) {
     ctx->sp_epoch = 1;
     fresh = true;
   }
   if (fresh && hipMemsetAsync(ctx->sp_status.p, 0, ctx->sp_status.cap * 8, s) != hipSuccess) return CPK_EDEVICE;
-  uint64_t *ustate = ctx->sp_status.p + ucap;
-  const uint64_t *utab = nullptr, *nunits = nullptr;
-  if (units) {
-    // unit counts -> starts (e4 scan) -> unit table
-    const uint32_t nb = scan_blocks(n);
-    if (int rc = reserve(ctx->sp_units, (uint64_t)n + (n + 1) + nb + 1 + units)) return rc;
-    uint64_t *ucnt = ctx->sp_units.p, *ustart = ucnt + n, *bsum = ustart + (n + 1), *tab = bsum + nb + 1;
-    const unsigned tb = 256, tg = (n + tb - 1) / tb;
-    hipLaunchKernelGGL(cpk::sp_units_count_kernel, dim3(tg), dim3(tb), 0, s, d_swo, pdesc, n, hint, ucnt);
-    scan_launch(ucnt, n, bsum, ustart, s);
-    hipLaunchKernelGGL(cpk::sp_units_fill_kernel, dim3(tg), dim3(tb), 0, s, (const uint64_t *)ustart, n, tab);
-    utab = tab;
-    nunits = ustart + n;
-  }
+  P.status = ctx->sp_status.p;
+  P.ustate = P.status + P.ucap;
+  P.epoch = ctx->sp_epoch;
+  P.utab = P.nunits = nullptr;
+  if (!units) return CPK_OK;
+  // unit counts -> starts (e4 scan) -> unit table
+  uint64_t *ucnt, *ustart, *bsum, *tab;
+  if (int rc = carve_reserve(ctx->sp_units, 0, [&](Carve &c) {
+        ucnt = c.take(n);
+        ustart = c.take((uint64_t)n + 1);
+        bsum = c.take(scan_blocks(n) + 1);
+        tab = c.take(units);
+      }))
+    return rc;
+  const unsigned tb = 256, tg = (n + tb - 1) / tb;
+  hipLaunchKernelGGL(cpk::sp_units_count_kernel, dim3(tg), dim3(tb), 0, s, d_swo, pdesc, n, hint, ucnt);
+  scan_launch(ucnt, n, bsum, ustart, s);
+  hipLaunchKernelGGL(cpk::sp_units_fill_kernel, dim3(tg), dim3(tb), 0, s, (const uint64_t *)ustart, n, tab);
+  P.utab = tab;
+  P.nunits = ustart + n;
+  return CPK_OK;
+}
+// the persistent grid of a plan's kernel: wpe workgroups per CU, never more than the units
+static unsigned sp_grid(cpk_ctx ctx, int wpe, const SpPlan &P) {
+  const uint64_t grid = (uint64_t)wpe * ctx->cus;
+  return (unsigned)(grid > P.ucap ? P.ucap : grid);
+}
+
+int sp_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, const uint64_t *pdesc,
+              const uint64_t *tin, uint32_t n, uint64_t hint, void *d_out, uint64_t *d_out_off,
+              hipStream_t s, bool gated = false, uint64_t units = 0, uint64_t out_cap = ~0ull) {
+  SpPlan P;
+  if (int rc = sp_plan(ctx, d_swo, pdesc, n, hint, units, s, P)) return rc;
   // (gated: the ticket was set by e4_gate_kernel -- exhausted unless the
   // batch is the single pass's)
   if (!gated && hipMemsetAsync(ctx->tickets + cpk::kTkPlan, 0, 4, s) != hipSuccess) return CPK_EDEVICE;
   // (gated: both forms enqueued, the one the gate did not pick returns at once)
-  const uint32_t *pick = gated ? ctx->tickets + cpk::kTkGate + 6 : nullptr;
-  constexpr uint32_t kLds = cpk::SpLay<cpk::SpDense>::kLds;
-  unsigned grid = (unsigned)(cpk::SpDense::kWpe * ctx->cus);
-  if (grid > ucap) grid = (unsigned)ucap;
-  if (pdesc)
-    hipLaunchKernelGGL(cpk::sp_encode_kernel<true>, dim3(grid), dim3(cpk::kSpThreads), kLds, s,
-                       (const uint64_t *)d_in, d_swo, pdesc, tin, n, (uint8_t *)d_out, d_out_off,
-                       ctx->sp_status.p, ctx->sp_epoch, ctx->tickets + cpk::kTkPlan, utab, nunits, ustate, hint,
-                       ctx->tickets + cpk::kTkErr, tin ? tin - 1 : (const uint64_t *)nullptr, pick, 0u, out_cap);
-  else
-    hipLaunchKernelGGL(cpk::sp_encode_kernel<false>, dim3(grid), dim3(cpk::kSpThreads), kLds, s,
-                       (const uint64_t *)d_in, d_swo, pdesc, tin, n, (uint8_t *)d_out, d_out_off,
-                       ctx->sp_status.p, ctx->sp_epoch, ctx->tickets + cpk::kTkPlan, utab, nunits, ustate, hint,
-                       ctx->tickets + cpk::kTkErr, tin ? tin - 1 : (const uint64_t *)nullptr, pick, 0u, out_cap);
-  if (gated && !pdesc) {
-    unsigned g2 = (unsigned)(cpk::SpSparse::kWpe * ctx->cus);
-    if (g2 > ucap) g2 = (unsigned)ucap;
-    hipLaunchKernelGGL((cpk::sp_encode_kernel<false, cpk::SpSparse>), dim3(g2), dim3(cpk::kSpThreads),
-                       cpk::SpLay<cpk::SpSparse>::kLds, s, (const uint64_t *)d_in, d_swo, pdesc, tin, n,
-                       (uint8_t *)d_out, d_out_off, ctx->sp_status.p, ctx->sp_epoch, ctx->tickets + cpk::kTkPlan, utab,
-                       nunits, ustate, hint, ctx->tickets + cpk::kTkErr, (const uint64_t *)nullptr, pick, 1u, out_cap);
-  }
+  const uint32_t *pick = gated ? ctx->tickets + cpk::kTkGate + cpk::kGateSparse : nullptr;
+  // (tin: the tables' words of a message batch, the output bound before them)
+  const uint64_t *bound = tin ? tin - 1 : nullptr;
+  auto launch = [&](auto kernel, int wpe, uint32_t lds, uint32_t form) {
+    hipLaunchKernelGGL(kernel, dim3(sp_grid(ctx, wpe, P)), dim3(cpk::kSpThreads), lds, s, (const uint64_t *)d_in,
+                       d_swo, pdesc, tin, n, (uint8_t *)d_out, d_out_off, P.status, P.epoch,
+                       ctx->tickets + cpk::kTkPlan, P.utab, P.nunits, P.ustate, hint, ctx->tickets + cpk::kTkErr, bound,
+                       pick, form, out_cap);
+  };
+  launch(pdesc ? cpk::sp_encode_kernel<true> : cpk::sp_encode_kernel<false>, cpk::SpDense::kWpe,
+         cpk::SpLay<cpk::SpDense>::kLds, 0u);
+  if (gated && !pdesc)
+    launch(cpk::sp_encode_kernel<false, cpk::SpSparse>, cpk::SpSparse::kWpe, cpk::SpLay<cpk::SpSparse>::kLds, 1u);
   return hip_ok(hipGetLastError());
-}
-
-// a bound on the units of n pieces of at most `hint` words (0: every piece
-// one unit); over 2^32 units: unsupported
-static uint64_t sp_unit_bound(uint64_t n, uint64_t hint) {
-  if (hint <= 64ull * cpk::kSpCS) return 0;
-  const uint64_t per = (hint + 64ull * cpk::kSpCS - 1) / (64ull * cpk::kSpCS);
-  return n * per;
 }
 
 // The size pass's rows for the emit pass (kE4RowBytes per 64-word step):
@@ -470,42 +526,124 @@ static int e4_rows(cpk_ctx ctx, const uint64_t *d_swo, uint32_t n, uint64_t hint
 // leaves each 64-word step's run boundaries for the emit pass: `stride` rows
 // per piece from the hint, or packed by word offset when there is no hint (the
 // batch's word count is then read back, synchronising the stream).
+// The two passes' kernels, each launched from here alone.  rows: whether the
+// size pass keeps its boundary rows (e4_rows, `stride`) for an emit pass;
+// skip: a device gate's word (nonzero: the other form took the batch), or
+// null; order: the pieces largest first, or null.
+static void e4_size_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, uint64_t hint,
+                           uint64_t *sizes, bool rows, uint64_t stride, const uint32_t *skip,
+                           const uint32_t *order, hipStream_t s) {
+  hipLaunchKernelGGL(rows ? cpk::e4_size_kernel<true> : cpk::e4_size_kernel<false>, dim3(e4_grid(ctx, n)),
+                     dim3(cpk::kE4Threads), 0, s, (const uint64_t *)d_in, d_swo, n, sizes,
+                     ctx->tickets + cpk::kTkEnc, hint, ctx->tickets + cpk::kTkErr,
+                     rows ? ctx->e4_bv.p : (uint64_t *)nullptr, rows ? stride : (uint64_t)0, skip, order);
+}
+// (off: the pieces' output offsets; sizes: the size pass's)
+static void e4_emit_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, const uint64_t *off,
+                           const uint64_t *sizes, uint64_t stride, const uint32_t *skip, const uint32_t *order,
+                           void *d_out, uint64_t out_cap, hipStream_t s) {
+  hipLaunchKernelGGL(cpk::e4_emit_kernel, dim3(e4_grid(ctx, n)), dim3(cpk::kE4Threads), cpk::kE4Lds, s,
+                     (const uint64_t *)d_in, d_swo, n, off, (uint8_t *)d_out, ctx->tickets + cpk::kTkDec,
+                     (const uint64_t *)ctx->e4_bv.p, stride, skip, sizes, out_cap, ctx->tickets + cpk::kTkErr, order);
+}
+
+// Arms a device gate over the piece sizes (e4_gate_kernel, sz_gate_kernel):
+// the gate block's min / max words preset and e4_minmax_kernel over the
+// batch; sampled: it also samples the words at d_in (their counts are
+// cleared first).  -> the samples taken
+static int gate_arm(cpk_ctx ctx, const uint64_t *d_swo, uint32_t n, bool sampled, const void *d_in, hipStream_t s,
+                    uint32_t &samples) {
+  uint32_t *mm = ctx->tickets + cpk::kTkGate;
+  if (hipMemsetAsync(mm + cpk::kGateMin, 0xff, 4, s) != hipSuccess ||
+      hipMemsetAsync(mm + cpk::kGateMax, 0, 4, s) != hipSuccess)
+    return CPK_EDEVICE;
+  if (sampled && (hipMemsetAsync(mm + cpk::kGateZero, 0, 4, s) != hipSuccess ||
+                  hipMemsetAsync(mm + cpk::kGateBytes, 0, 4, s) != hipSuccess))
+    return CPK_EDEVICE;
+  const unsigned mg = n < 256u * 256u ? (unsigned)((n + 255) / 256) : 256u;
+  hipLaunchKernelGGL(cpk::e4_minmax_kernel, dim3(mg), dim3(256), 0, s, d_swo, n, mm,
+                     sampled ? (const uint64_t *)d_in : (const uint64_t *)nullptr);
+  samples = mg * 256u;
+  return CPK_OK;
+}
+
 int e4_encode(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, uint64_t hint,
               void *d_out, uint64_t *d_out_off, hipStream_t s, bool gate = false, uint64_t out_cap = ~0ull) {
-  int rc = reserve(ctx->status, (uint64_t)n + scan_blocks(n) + 1, 1024);
-  if (rc) return rc;
-  uint64_t stride;
-  rc = e4_rows(ctx, d_swo, n, hint, s, stride);
-  if (rc) return rc;
-  uint64_t *sizes = ctx->status.p, *bsum = ctx->status.p + n;
-  if (hipMemsetAsync(ctx->tickets, 0, cpk::kTkErr * 4, s) != hipSuccess) return CPK_EDEVICE;
+  uint64_t *sizes, *bsum, stride;
+  if (int rc = sizes_scratch(ctx, n, sizes, bsum)) return rc;
+  if (int rc = e4_rows(ctx, d_swo, n, hint, s, stride)) return rc;
+  if (enc_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
+  const uint32_t *skip = nullptr;
   if (gate) {
     // which encoder takes the batch, decided on the device from the piece
     // sizes (no host sync): the other's tickets are exhausted, so its
     // kernels return at once (the scans then write offsets the single pass
     // overwrites)
-    uint32_t *mm = ctx->tickets + cpk::kTkGate;
-    if (hipMemsetAsync(mm, 0xff, 4, s) != hipSuccess || hipMemsetAsync(mm + 1, 0, 4, s) != hipSuccess ||
-        hipMemsetAsync(mm + 3, 0, 4, s) != hipSuccess || hipMemsetAsync(mm + 7, 0, 4, s) != hipSuccess)
-      return CPK_EDEVICE;
-    const unsigned mg = n < 256u * 256u ? (unsigned)((n + 255) / 256) : 256u;
-    hipLaunchKernelGGL(cpk::e4_minmax_kernel, dim3(mg), dim3(256), 0, s, d_swo, n, mm, (const uint64_t *)d_in);
-    hipLaunchKernelGGL(cpk::e4_gate_kernel, dim3(1), dim3(64), 0, s, ctx->tickets, mg * 256u, (uint32_t)ctx->sp_form,
+    uint32_t samples;
+    if (int rc = gate_arm(ctx, d_swo, n, true, d_in, s, samples)) return rc;
+    hipLaunchKernelGGL(cpk::e4_gate_kernel, dim3(1), dim3(64), 0, s, ctx->tickets, samples, (uint32_t)ctx->sp_form,
                        d_swo, n);
+    skip = ctx->tickets + cpk::kTkGate + cpk::kGatePick;
   }
-  const unsigned grid = e4_grid(ctx, n);
-  hipLaunchKernelGGL(cpk::e4_size_kernel<true>, dim3(grid), dim3(cpk::kE4Threads), 0, s,
-                     (const uint64_t *)d_in, d_swo, n, sizes, ctx->tickets + cpk::kTkEnc, hint,
-                     ctx->tickets + cpk::kTkErr, ctx->e4_bv.p, stride,
-                     gate ? (const uint32_t *)(ctx->tickets + cpk::kTkGate + 2) : (const uint32_t *)nullptr,
-                     (const uint32_t *)nullptr);
+  e4_size_launch(ctx, d_in, d_swo, n, hint, sizes, true, stride, skip, nullptr, s);
   scan_launch(sizes, n, bsum, d_out_off, s);
-  hipLaunchKernelGGL(cpk::e4_emit_kernel, dim3(grid), dim3(cpk::kE4Threads), cpk::kE4Lds, s,
-                     (const uint64_t *)d_in, d_swo, n, (const uint64_t *)d_out_off,
-                     (uint8_t *)d_out, ctx->tickets + cpk::kTkDec, (const uint64_t *)ctx->e4_bv.p,
-                     stride, gate ? (const uint32_t *)(ctx->tickets + cpk::kTkGate + 2) : (const uint32_t *)nullptr,
-                     (const uint64_t *)sizes, out_cap, ctx->tickets + cpk::kTkErr, (const uint32_t *)nullptr);
+  e4_emit_launch(ctx, d_in, d_swo, n, d_out_off, sizes, stride, skip, nullptr, d_out, out_cap, s);
   return hip_ok(hipGetLastError());
+}
+
+// The front half of the two passes over a message batch: d_out_off = the
+// pieces' packed offsets in message order (a table per message, then its
+// segments).  rows: an emit pass follows -- the size pass keeps its boundary
+// rows (e4_rows, which without a hint synchronises the stream) and the
+// segments' output offsets get room.  Segments are taken largest first (a
+// wave takes a whole segment, and a 256 KiB one taken last kept the rest of
+// the chip idle behind it): by CPK_E4_ORDER=1 in both passes, =2 in the emit
+// pass only.
+struct MsgPass {
+  uint64_t *ssize, *tsize;  // the segments' and the tables' packed sizes
+  uint64_t *soff;           // the segments' output offsets, for msg_table_emit_kernel to write (rows only)
+  const uint32_t *order;    // the segments largest first, or null
+  uint64_t stride;          // e4_rows (rows only)
+};
+static int msg_front(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t nseg,
+                     const uint64_t *d_msg_seg_off, uint32_t nm, uint64_t hint, uint64_t *d_out_off, hipStream_t s,
+                     bool rows, MsgPass &M) {
+  const uint64_t np = (uint64_t)nm + nseg;
+  uint64_t *comb, *bsum;
+  uint32_t *sord, *shist;
+  if (int rc = carve_reserve(ctx->status, 1024, [&](Carve &c) {
+        M.ssize = c.take(nseg);
+        M.tsize = c.take(nm);
+        comb = c.take(np);  // both, in message order
+        M.soff = rows ? c.take(nseg) : nullptr;
+        bsum = c.take(scan_blocks(np) + 1);
+        sord = c.take32(nseg);
+        shist = c.take32(cpk::kOrdClasses);
+        // (the order has always been given nseg / 2 + 1 entries, one more than
+        // an even nseg needs: kept, so the size asked for is what it was)
+        const uint64_t spare = nseg & 1 ? 0 : 1;
+        c.take(spare);
+      }))
+    return rc;
+  M.stride = 0;
+  if (rows)
+    if (int rc = e4_rows(ctx, d_swo, nseg, hint, s, M.stride)) return rc;
+  if (enc_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
+  M.order = nullptr;
+  if (nseg && (ctx->e4_order == 1 || (rows && ctx->e4_order))) {
+    ord_launch(nullptr, nseg, shist, sord, s, d_swo);
+    M.order = sord;
+  }
+  if (nseg)
+    e4_size_launch(ctx, d_in, d_swo, nseg, hint, M.ssize, rows, M.stride, nullptr,
+                   ctx->e4_order == 1 ? M.order : nullptr, s);
+  // the tables, sized as msg_table_emit_kernel builds them
+  const unsigned tb = 256, tg = (nm + tb - 1) / tb;
+  hipLaunchKernelGGL(cpk::msg_table_size_kernel, dim3(tg), dim3(tb), 0, s, d_swo, d_msg_seg_off, nm, M.tsize);
+  hipLaunchKernelGGL(cpk::msg_interleave_kernel, dim3(tg), dim3(tb), 0, s, d_msg_seg_off, nm,
+                     (const uint64_t *)M.tsize, (const uint64_t *)M.ssize, comb);
+  scan_launch(comb, (uint32_t)np, bsum, d_out_off, s);
+  return CPK_OK;
 }
 
 int cpk_encode_messages(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t nseg,
@@ -542,46 +680,13 @@ int cpk_encode_messages_cap(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo
     return sp_launch(ctx, d_in, nullptr, pdesc, tbuf, (uint32_t)np, max_seg_words, d_out, d_out_off, s, false, ub,
                      out_cap);
   }
-  const uint32_t nb = scan_blocks(np);
-  // scratch: segment sizes | table sizes | message-order sizes | segment offsets | block sums |
-  // the segments largest first (u32) | their class counts (u32)
-  int rc = reserve(ctx->status, (uint64_t)nseg + nm + np + nseg + nb + 1 + nseg / 2 + 1 + cpk::kOrdClasses / 2, 1024);
-  if (rc) return rc;
-  uint64_t *ssize = ctx->status.p, *tsize = ssize + nseg, *comb = tsize + nm, *soff = comb + np;
-  uint64_t *bsum = soff + nseg;
-  uint32_t *sord = reinterpret_cast<uint32_t *>(bsum + nb + 1), *shist = sord + nseg + (nseg & 1);
-  uint64_t stride;
-  rc = e4_rows(ctx, d_swo, nseg, max_seg_words, s, stride);
-  if (rc) return rc;
-  if (hipMemsetAsync(ctx->tickets, 0, cpk::kTkErr * 4, s) != hipSuccess) return CPK_EDEVICE;
+  MsgPass M;
+  if (int rc = msg_front(ctx, d_in, d_swo, nseg, d_msg_seg_off, nm, max_seg_words, d_out_off, s, true, M)) return rc;
   const unsigned tb = 256, tg = (nm + tb - 1) / tb;
-  const unsigned grid = e4_grid(ctx, nseg);
-  // (segments largest first, both passes: a wave takes a whole segment, and a
-  // 256 KiB one taken last kept the rest of the chip idle behind it)
-  const uint32_t *order = nullptr;
-  if (nseg && ctx->e4_order) {
-    ord_launch(nullptr, nseg, shist, sord, s, d_swo);
-    order = sord;
-  }
-  const uint32_t *size_order = ctx->e4_order == 1 ? order : nullptr;
-  if (nseg)
-    hipLaunchKernelGGL(cpk::e4_size_kernel<true>, dim3(grid), dim3(cpk::kE4Threads), 0, s,
-                       (const uint64_t *)d_in, d_swo, nseg, ssize, ctx->tickets + cpk::kTkEnc,
-                       max_seg_words, ctx->tickets + cpk::kTkErr, ctx->e4_bv.p, stride, (const uint32_t *)nullptr,
-                       size_order);
-  hipLaunchKernelGGL(cpk::msg_table_size_kernel, dim3(tg), dim3(tb), 0, s, d_swo, d_msg_seg_off, nm,
-                     tsize);
-  hipLaunchKernelGGL(cpk::msg_interleave_kernel, dim3(tg), dim3(tb), 0, s, d_msg_seg_off, nm,
-                     (const uint64_t *)tsize, (const uint64_t *)ssize, comb);
-  scan_launch(comb, (uint32_t)np, bsum, d_out_off, s);
   hipLaunchKernelGGL(cpk::msg_table_emit_kernel, dim3(tg), dim3(tb), 0, s, d_swo, d_msg_seg_off, nm,
-                     (const uint64_t *)d_out_off, soff, (uint8_t *)d_out, (const uint64_t *)tsize, out_cap,
+                     (const uint64_t *)d_out_off, M.soff, (uint8_t *)d_out, (const uint64_t *)M.tsize, out_cap,
                      ctx->tickets + cpk::kTkErr);
-  if (nseg)
-    hipLaunchKernelGGL(cpk::e4_emit_kernel, dim3(grid), dim3(cpk::kE4Threads), cpk::kE4Lds, s,
-                       (const uint64_t *)d_in, d_swo, nseg, (const uint64_t *)soff, (uint8_t *)d_out,
-                       ctx->tickets + cpk::kTkDec, (const uint64_t *)ctx->e4_bv.p, stride, (const uint32_t *)nullptr,
-                       (const uint64_t *)ssize, out_cap, ctx->tickets + cpk::kTkErr, order);
+  if (nseg) e4_emit_launch(ctx, d_in, d_swo, nseg, M.soff, M.ssize, M.stride, nullptr, M.order, d_out, out_cap, s);
   return hip_ok(hipGetLastError());
 }
 
@@ -601,15 +706,8 @@ int cpk_encode_batch_cap(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, u
     return e4_encode(ctx, d_in, d_swo, n, max_seg_words, d_out, d_out_off, s, false, out_cap);
   if (ctx->encoder == 0) {
     // (forced single pass: pieces of any size, several units for a large one)
-    uint64_t hint = max_seg_words;
-    if (!hint) {  // (no bound given: the batch's words bound every piece)
-      uint64_t ends[2];
-      int rc = read_words(ctx, s, {d_swo, d_swo + n}, ends);
-      if (rc) return rc;
-      hint = ends[1] - ends[0];
-    }
-    uint64_t ub = sp_unit_bound(n, hint);
-    if (hint > 64ull * cpk::kSpCS && !max_seg_words) ub = n + hint / (64ull * cpk::kSpCS) + 1;
+    uint64_t ub;
+    if (int rc = sp_batch_unit_bound(ctx, d_swo, n, max_seg_words, s, ub)) return rc;
     if (ub > 0xffffffffull) return CPK_EUNSUPPORTED;
     return sp_launch(ctx, d_in, d_swo, nullptr, nullptr, n, max_seg_words, d_out, d_out_off, s, false, ub,
                      out_cap);
@@ -623,16 +721,9 @@ int cpk_encode_batch_cap(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, u
 }
 
 // ---- exact packed sizes without encoding (encode_size.hip) -----------------
-// The wave-per-piece size walk without boundary rows: sizes[i] = piece i's
-// packed bytes.  skip: the device gate's word (nonzero: the other form took
-// the batch); order: the pieces largest first, or null.
-static void size_walk_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, uint64_t hint,
-                             uint64_t *sizes, const uint32_t *skip, const uint32_t *order, hipStream_t s) {
-  hipLaunchKernelGGL(cpk::e4_size_kernel<false>, dim3(e4_grid(ctx, n)), dim3(cpk::kE4Threads), 0, s,
-                     (const uint64_t *)d_in, d_swo, n, sizes, ctx->tickets + cpk::kTkEnc, hint,
-                     ctx->tickets + cpk::kTkErr, (uint64_t *)nullptr, (uint64_t)0, skip, order);
-}
-
+// Two forms, both enqueued for the device to choose (sz_gate_kernel): the
+// chunk-parallel one over the single pass's plan (sp_plan), and the two
+// passes' wave-per-piece size walk without boundary rows.
 int cpk_packed_size_batch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n,
                           uint64_t max_seg_words, uint64_t *d_out_off, void *stream) {
   if (!ctx || (!d_swo && n) || !d_out_off) return CPK_EINVAL;
@@ -644,60 +735,28 @@ int cpk_packed_size_batch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, 
   // hint, or from the batch's word count read back (synchronising the stream,
   // as cpk_encode_batch without a hint).  The chunk-parallel form is enqueued
   // (for the device to choose) when its unit table stays of bounded size.
-  uint64_t ub = sp_unit_bound(n, max_seg_words);
-  if (!max_seg_words) {
-    uint64_t ends[2];
-    int rc = read_words(ctx, s, {d_swo, d_swo + n}, ends);
-    if (rc) return rc;
-    const uint64_t total = ends[1] - ends[0];
-    ub = total > 64ull * cpk::kSpCS ? n + total / (64ull * cpk::kSpCS) + 1 : 0;
-  }
+  uint64_t ub;
+  if (int rc = sp_batch_unit_bound(ctx, d_swo, n, max_seg_words, s, ub)) return rc;
   const bool can_chunk = ctx->size_form != 2 && ub <= (1ull << 25);
-  const uint32_t nb = scan_blocks(n);
-  int rc = reserve(ctx->status, (uint64_t)n + nb + 1, 1024);
-  if (rc) return rc;
-  uint64_t *sizes = ctx->status.p, *bsum = sizes + n;
-  uint32_t *mm = ctx->tickets + cpk::kTkGate;
-  if (hipMemsetAsync(ctx->tickets, 0, cpk::kTkErr * 4, s) != hipSuccess ||
-      hipMemsetAsync(sizes, 0, (uint64_t)n * 8, s) != hipSuccess || hipMemsetAsync(mm, 0xff, 4, s) != hipSuccess ||
-      hipMemsetAsync(mm + 1, 0, 4, s) != hipSuccess)
+  uint64_t *sizes, *bsum;
+  if (int rc = sizes_scratch(ctx, n, sizes, bsum)) return rc;
+  if (enc_tickets_reset(ctx, s) != hipSuccess || hipMemsetAsync(sizes, 0, (uint64_t)n * 8, s) != hipSuccess)
     return CPK_EDEVICE;
   // the form, decided on the device from the piece sizes (no host sync, no
   // sample of the words)
-  const unsigned mg = n < 256u * 256u ? (unsigned)((n + 255) / 256) : 256u;
-  hipLaunchKernelGGL(cpk::e4_minmax_kernel, dim3(mg), dim3(256), 0, s, d_swo, n, mm, (const uint64_t *)nullptr);
+  uint32_t samples;
+  if (int rc = gate_arm(ctx, d_swo, n, false, nullptr, s, samples)) return rc;
   hipLaunchKernelGGL(cpk::sz_gate_kernel, dim3(1), dim3(64), 0, s, ctx->tickets, d_swo, n, can_chunk ? 1u : 0u,
                      (uint32_t)ctx->size_form);
   if (can_chunk) {
-    const uint64_t ucap = ub ? ub : n;
-    // the units' run-state words, epoch-tagged as the single pass's (sp_launch)
-    bool fresh = false;
-    if ((rc = reserve(ctx->sp_status, 2 * ucap, 8192, nullptr, &fresh))) return rc;
-    if (++ctx->sp_epoch > 0xffffu) {
-      ctx->sp_epoch = 1;
-      fresh = true;
-    }
-    if (fresh && hipMemsetAsync(ctx->sp_status.p, 0, ctx->sp_status.cap * 8, s) != hipSuccess) return CPK_EDEVICE;
-    const uint64_t *utab = nullptr, *nunits = nullptr;
-    if (ub) {
-      // unit counts -> starts (e4 scan) -> unit table (sp_launch)
-      if ((rc = reserve(ctx->sp_units, (uint64_t)n + (n + 1) + nb + 1 + ub))) return rc;
-      uint64_t *ucnt = ctx->sp_units.p, *ustart = ucnt + n, *ubsum = ustart + (n + 1), *tab = ubsum + nb + 1;
-      const unsigned tb = 256, tg = (n + tb - 1) / tb;
-      hipLaunchKernelGGL(cpk::sp_units_count_kernel, dim3(tg), dim3(tb), 0, s, d_swo, (const uint64_t *)nullptr, n,
-                         max_seg_words, ucnt);
-      scan_launch(ucnt, n, ubsum, ustart, s);
-      hipLaunchKernelGGL(cpk::sp_units_fill_kernel, dim3(tg), dim3(tb), 0, s, (const uint64_t *)ustart, n, tab);
-      utab = tab;
-      nunits = ustart + n;
-    }
-    unsigned grid = (unsigned)(cpk::kSzWpe * ctx->cus);
-    if (grid > ucap) grid = (unsigned)ucap;
-    hipLaunchKernelGGL(cpk::sz_chunk_kernel, dim3(grid), dim3(cpk::kSpThreads), 0, s, (const uint64_t *)d_in, d_swo,
-                       n, (unsigned long long *)sizes, ctx->tickets + cpk::kTkPlan, utab, nunits,
-                       ctx->sp_status.p + ucap, ctx->sp_epoch, max_seg_words, ctx->tickets + cpk::kTkErr);
+    SpPlan P;
+    if (int rc = sp_plan(ctx, d_swo, nullptr, n, max_seg_words, ub, s, P)) return rc;
+    hipLaunchKernelGGL(cpk::sz_chunk_kernel, dim3(sp_grid(ctx, cpk::kSzWpe, P)), dim3(cpk::kSpThreads), 0, s,
+                       (const uint64_t *)d_in, d_swo, n, (unsigned long long *)sizes, ctx->tickets + cpk::kTkPlan,
+                       P.utab, P.nunits, P.ustate, P.epoch, max_seg_words, ctx->tickets + cpk::kTkErr);
   }
-  size_walk_launch(ctx, d_in, d_swo, n, max_seg_words, sizes, ctx->tickets + cpk::kTkGate + 2, nullptr, s);
+  e4_size_launch(ctx, d_in, d_swo, n, max_seg_words, sizes, false, 0, ctx->tickets + cpk::kTkGate + cpk::kGatePick,
+                 nullptr, s);
   scan_launch(sizes, n, bsum, d_out_off, s);
   return hip_ok(hipGetLastError());
 }
@@ -712,29 +771,8 @@ int cpk_packed_size_messages(cpk_ctx ctx, const void *d_in, const uint64_t *d_sw
   if (nm == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
   const uint64_t np = (uint64_t)nm + nseg;  // pieces: a table per message + the segments
   if (np > 0xffffffffull) return CPK_EINVAL;
-  const uint32_t nb = scan_blocks(np);
-  // scratch: segment sizes | table sizes | message-order sizes | block sums |
-  // the segments largest first (u32) | their class counts (u32)
-  int rc = reserve(ctx->status, (uint64_t)nseg + nm + np + nb + 1 + nseg / 2 + 1 + cpk::kOrdClasses / 2, 1024);
-  if (rc) return rc;
-  uint64_t *ssize = ctx->status.p, *tsize = ssize + nseg, *comb = tsize + nm, *bsum = comb + np;
-  uint32_t *sord = reinterpret_cast<uint32_t *>(bsum + nb + 1), *shist = sord + nseg + (nseg & 1);
-  if (hipMemsetAsync(ctx->tickets, 0, cpk::kTkErr * 4, s) != hipSuccess) return CPK_EDEVICE;
-  const unsigned tb = 256, tg = (nm + tb - 1) / tb;
-  if (nseg) {
-    // (segments largest first, as cpk_encode_messages' size pass)
-    const uint32_t *order = nullptr;
-    if (ctx->e4_order == 1) {
-      ord_launch(nullptr, nseg, shist, sord, s, d_swo);
-      order = sord;
-    }
-    size_walk_launch(ctx, d_in, d_swo, nseg, max_seg_words, ssize, nullptr, order, s);
-  }
-  // the tables, built on the device as the encoder builds them, sized in place
-  hipLaunchKernelGGL(cpk::msg_table_size_kernel, dim3(tg), dim3(tb), 0, s, d_swo, d_msg_seg_off, nm, tsize);
-  hipLaunchKernelGGL(cpk::msg_interleave_kernel, dim3(tg), dim3(tb), 0, s, d_msg_seg_off, nm,
-                     (const uint64_t *)tsize, (const uint64_t *)ssize, comb);
-  scan_launch(comb, (uint32_t)np, bsum, d_out_off, s);
+  MsgPass M;
+  if (int rc = msg_front(ctx, d_in, d_swo, nseg, d_msg_seg_off, nm, max_seg_words, d_out_off, s, false, M)) return rc;
   return hip_ok(hipGetLastError());
 }
 
@@ -762,13 +800,16 @@ namespace {
 // forced: the by-density choice is made for batches, cpk_decode_batch)
 bool dec_v2(cpk_ctx ctx) { return ctx->decoder == 2; }
 
+// the context's choice, the block map, the record index, the block map's
+// dense form (decode_kernel<.., true>); the last three in the order of
+// dec_gate_kernel's skip words
+enum DecKind { kDecCtx, kDecMap, kDecIndex, kDecDense };
+
 void dec_launch(cpk_ctx ctx, bool stream, unsigned want, const uint8_t *packed, uint64_t *in_off,
                 const uint64_t *swo, uint32_t n, uint64_t *out, int32_t *status, uint64_t avail,
-                cpk::DecStreams sd, hipStream_t s, int which = 0) {
-  // which: 0 the context's choice, 1 the block map, 2 the record index, 3
-  // the block map's dense form (decode_kernel<.., true>)
-  const bool v2 = which ? which == 2 : dec_v2(ctx);
-  const bool dense = which == 3;
+                cpk::DecStreams sd, hipStream_t s, DecKind which = kDecCtx) {
+  const bool v2 = which == kDecCtx ? dec_v2(ctx) : which == kDecIndex;
+  const bool dense = which == kDecDense;
   const uint32_t lds = v2 ? cpk::kD2Lds : cpk::kDecLds;
   const unsigned per_cu = (unsigned)min(8u, 160u * 1024u / lds);
   unsigned grid = per_cu * (unsigned)ctx->cus;
@@ -815,12 +856,12 @@ static int decode_batch_impl(cpk_ctx ctx, const void *d_packed, const uint64_t *
   uint64_t *in_off = const_cast<uint64_t *>(d_in_off);
   if (ctx->decoder != 3) {
     dec_launch(ctx, false, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out,
-               d_status, 0, cpk::DecStreams{nullptr, nullptr, nullptr, 0, nullptr, nullptr}, s);
+               d_status, 0, cpk::DecStreams::batch(), s);
     return hip_ok(hipGetLastError());
   }
-  // by density, decided on the device (dec_gate_kernel): both enqueued, the
-  // one not chosen returns at its first instruction
-  uint32_t *skip = ctx->tickets + cpk::kTkGate + 8;  // [3]: block map, record index, dense block map
+  // by density, decided on the device (dec_gate_kernel): all three enqueued,
+  // the ones not chosen return at their first instruction
+  uint32_t *skip = ctx->tickets + cpk::kTkGate + cpk::kGateDecSkip;  // [3]: kDecMap, kDecIndex, kDecDense
   hipLaunchKernelGGL(cpk::dec_gate_kernel, dim3(1), dim3(64), 0, s, (const uint64_t *)d_in_off, d_swo, n, skip);
   if (probe && n <= 32) {
     // A few pieces: read their extent back (one sync).  With >= 8 MiB of
@@ -845,12 +886,9 @@ static int decode_batch_impl(cpk_ctx ctx, const void *d_packed, const uint64_t *
         return CPK_EDEVICE;
     }
   }
-  dec_launch(ctx, false, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out, d_status, 0,
-             cpk::DecStreams{nullptr, nullptr, nullptr, 0, nullptr, skip}, s, 1);
-  dec_launch(ctx, false, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out, d_status, 0,
-             cpk::DecStreams{nullptr, nullptr, nullptr, 0, nullptr, skip + 1}, s, 2);
-  dec_launch(ctx, false, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out, d_status, 0,
-             cpk::DecStreams{nullptr, nullptr, nullptr, 0, nullptr, skip + 2}, s, 3);
+  for (int k = kDecMap; k <= kDecDense; ++k)
+    dec_launch(ctx, false, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out, d_status, 0,
+               cpk::DecStreams::batch(skip + (k - kDecMap)), s, (DecKind)k);
   return hip_ok(hipGetLastError());
 }
 
@@ -894,40 +932,31 @@ uint64_t ss_reach(uint64_t avail, uint64_t words) {
 int ss_bufs(cpk_ctx ctx, uint64_t nb, cpk::SsBufs &B) {
   using namespace cpk;
   const uint64_t ng = (nb + kSsGroup - 1) / kSsGroup;
-  // scratch layout (u64 entries)
-  const uint64_t need = 5 * nb + 3 * kSsCand * nb + (nb + 1) / 2 + 3 * kSsVar * ng + (kSsVar + 1) * nb +
-                        ((kSsVar + 1) * nb + 1) / 2 + (ng + 1) / 2 + ng + 4 * (nb + 1) + (nb + 1) / 2 + 2 + 2;
-  if (int rc = reserve(ctx->ss_buf, need)) return rc;
-  uint64_t *q = ctx->ss_buf.p;
-  auto take = [&](uint64_t k) {
-    uint64_t *r = q;
-    q += k;
-    return r;
-  };
-  B.X = take(nb);
-  B.W = take(nb);
-  B.C1 = take(nb);
-  B.L1 = take(nb);
-  B.WL1 = take(nb);
-  B.C2 = take(kSsCand * nb);
-  B.L2 = take(kSsCand * nb);
-  B.WL2 = take(kSsCand * nb);
-  B.N2 = (uint32_t *)take((nb + 1) / 2);
-  B.GE = take(kSsVar * ng);
-  B.GX = take(kSsVar * ng);
-  B.GW = take(kSsVar * ng);
-  B.VE = take((kSsVar + 1) * nb);
-  B.VW = (uint32_t *)take(((kSsVar + 1) * nb + 1) / 2);
-  B.GC = (uint32_t *)take((ng + 1) / 2);
-  B.GB = take(ng);
-  B.E = take(nb + 1);
-  B.WO = take(nb + 1);
-  B.sin = take(nb + 1);
-  B.sswo = take(nb + 1);
-  B.sst = (int32_t *)take((nb + 1) / 2);
-  B.flag = (uint32_t *)take(2);
-  B.lim = take(2);
-  return CPK_OK;
+  return carve_reserve(ctx->ss_buf, 0, [&](Carve &c) {
+    B.X = c.take(nb);
+    B.W = c.take(nb);
+    B.C1 = c.take(nb);
+    B.L1 = c.take(nb);
+    B.WL1 = c.take(nb);
+    B.C2 = c.take(kSsCand * nb);
+    B.L2 = c.take(kSsCand * nb);
+    B.WL2 = c.take(kSsCand * nb);
+    B.N2 = c.take32(nb);
+    B.GE = c.take(kSsVar * ng);
+    B.GX = c.take(kSsVar * ng);
+    B.GW = c.take(kSsVar * ng);
+    B.VE = c.take((kSsVar + 1) * nb);
+    B.VW = c.take32((kSsVar + 1) * nb);
+    B.GC = c.take32(ng);
+    B.GB = c.take(ng);
+    B.E = c.take(nb + 1);
+    B.WO = c.take(nb + 1);
+    B.sin = c.take(nb + 1);
+    B.sswo = c.take(nb + 1);
+    B.sst = (int32_t *)c.take32(nb);
+    B.flag = c.take32(4);
+    B.lim = c.take(2);
+  });
 }
 
 // parallel stream decode over at most `reach` bytes; enqueues the one-wave
@@ -946,13 +975,12 @@ int ss_decode(cpk_ctx ctx, const uint8_t *pk, uint64_t avail, uint64_t reach, co
   hipLaunchKernelGGL(ss_sub_kernel, dim3((unsigned)((nsub + 1 + tb - 1) / tb)), dim3(tb), 0, s, swo, n, nb,
                      (const uint64_t *)in_off, B);
   dec_launch(ctx, false, (unsigned)((nsub + 3) / 4), pk, B.sin, B.sswo, (uint32_t)nsub, out, B.sst, 0,
-             DecStreams{nullptr, nullptr, nullptr, 0, nullptr}, s);
+             DecStreams::batch(), s);
   hipLaunchKernelGGL(ss_check_kernel, dim3((unsigned)((nsub + tb - 1) / tb)), dim3(tb), 0, s, nsub, B);
   hipLaunchKernelGGL(ss_final_kernel, dim3((n + tb - 1) / tb), dim3(tb), 0, s, n, status, ctx->tickets + kTkDec, B,
                      getenv("CPK_STREAM_NO_FALLBACK") ? 1 : 0);
   // the one-wave decoder: no ticket unless the parallel path gave up
-  dec_launch(ctx, true, 1, pk, in_off, swo, n, out, status, avail,
-             DecStreams{nullptr, nullptr, nullptr, 1, in_off + n}, s);
+  dec_launch(ctx, true, 1, pk, in_off, swo, n, out, status, avail, DecStreams::one(in_off + n), s);
   return hip_ok(hipGetLastError());
 }
 }  // namespace
@@ -986,7 +1014,7 @@ int cpk_decode_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
     return CPK_EDEVICE;
   // one stream: one wave works, the others find no ticket
   dec_launch(ctx, true, 1, (const uint8_t *)d_packed, d_in_off, d_swo, n, (uint64_t *)d_out, d_status, avail,
-             cpk::DecStreams{nullptr, nullptr, nullptr, 1, d_in_off + n}, s);
+             cpk::DecStreams::one(d_in_off + n), s);
   return hip_ok(hipGetLastError());
 }
 
@@ -1024,6 +1052,10 @@ int cpk_decode_message_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
   // the chain's entries: a message per 64 packed bytes to begin with
   auto ms_bufs = [&](uint64_t entries, MsBufs &M) -> int {
     // ctl [8] | result row [8] | X, S, P [cap each] | statuses [cap x i32]
+    // (not a Carve layout: this buffer's capacity counts chain entries, its
+    // bytes follow from the capacity reserve() settles on, and the kernels
+    // are told that capacity -- a layout counted before the reservation
+    // would need the count run a second time inside the bytes callback)
     if (int rc = reserve(ctx->ms_buf, entries, 0, [](uint64_t cap) { return (16 + 3 * cap + (cap + 1) / 2) * 8; }))
       return rc;
     M.mcap = ctx->ms_buf.cap;
@@ -1045,7 +1077,7 @@ int cpk_decode_message_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
   hipLaunchKernelGGL(ms_end_kernel, dim3(1), dim3(64), 0, s, pk, nb, out_cap_words, B, M);
   hipLaunchKernelGGL(ms_sub_kernel, dim3((unsigned)((nsub + 1 + tb - 1) / tb)), dim3(tb), 0, s, nb, B, M);
   dec_launch(ctx, false, (unsigned)((nsub + 3) / 4), pk, B.sin, B.sswo, (uint32_t)nsub, (uint64_t *)d_out, B.sst, 0,
-             DecStreams{nullptr, nullptr, nullptr, 0, nullptr}, s);
+             DecStreams::batch(), s);
   hipLaunchKernelGGL(ss_check_kernel, dim3((unsigned)((nsub + tb - 1) / tb)), dim3(tb), 0, s, nsub, B);
   uint64_t r[8];
   for (int attempt = 0;; ++attempt) {
@@ -1176,13 +1208,20 @@ static int read_message_impl(cpk_ctx ctx, const void *d_packed, uint64_t avail, 
   if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 7)) return CPK_EINVAL;
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
-  // swo [515] | in_off [515] | statuses [514 x i32] | stream descriptor [4] | stream end [1] | pieces [1]
-  // | spare [2] | info row [517]
-  if (int rc = reserve_fixed(ctx->rm_buf, (2 * (kRmPieces + 1) + kRmPieces / 2 + 8 + cpk::kRmInfo) * 8ull)) return rc;
-  if (!d_info) d_info = ctx->rm_buf.p + 2 * (kRmPieces + 1) + kRmPieces / 2 + 8;
-  uint64_t *swo = ctx->rm_buf.p, *in_off = swo + kRmPieces + 1;
-  int32_t *pst = (int32_t *)(in_off + kRmPieces + 1);
-  uint64_t *sdesc = in_off + kRmPieces + 1 + kRmPieces / 2, *send_out = sdesc + 4, *npad = sdesc + 5;
+  uint64_t *swo, *in_off, *sdesc, *send_out, *npad, *info_row;
+  int32_t *pst;
+  if (int rc = carve_reserve(ctx->rm_buf, 0, [&](Carve &c) {
+        swo = c.take(kRmPieces + 1);
+        in_off = c.take(kRmPieces + 1);
+        pst = (int32_t *)c.take32(kRmPieces);  // statuses
+        sdesc = c.take(4);                     // the stream descriptor
+        send_out = c.take(1);                  // the stream's end
+        npad = c.take(1);                      // pieces
+        c.take(2);                             // (spare)
+        info_row = c.take(cpk::kRmInfo);
+      }, true))
+    return rc;
+  if (!d_info) d_info = info_row;
   // the pieces' sizes are on the device only: the stream decoder is sized by
   // the bytes the caller's capacity can reach (10 per word at most)
   const uint64_t reach = ss_reach(avail, out_cap_words + cpk::kRmHead);
@@ -1227,7 +1266,7 @@ static int read_message_impl(cpk_ctx ctx, const void *d_packed, uint64_t avail, 
     // on the device: a one-stream descriptor), none of the padding; its
     // tickets were zeroed by rm_table_kernel
     dec_launch(ctx, true, 1, (const uint8_t *)d_packed, in_off, swo, kRmPieces, (uint64_t *)d_out, pst, avail,
-               cpk::DecStreams{sdesc, sdesc + 1, sdesc + 2, 1, send_out}, s);
+               cpk::DecStreams::one_desc(sdesc, send_out), s);
     rc = hip_ok(hipGetLastError());
   }
   if (rc) return rc;
@@ -1250,14 +1289,18 @@ int cpk_decode_messages(cpk_ctx ctx, const void *d_packed, const uint64_t *d_msg
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
   if (nm == 0) return hip_ok(hipMemsetAsync(d_msg_seg_off, 0, 8, s));
-  // scratch: words | begin | words offsets [nm+1] | block sums x2
-  const uint32_t nb = scan_blocks(nm);
-  // (+ the stream order: nm u32 and kOrdClasses u32)
-  int rc = reserve(ctx->status, 3ull * nm + 1 + 2ull * nb + (nm + 1) / 2 + cpk::kOrdClasses / 2, 1024);
-  if (rc) return rc;
-  uint64_t *mwords = ctx->status.p, *mbeg = mwords + nm, *mwoff = mbeg + nm;
-  uint64_t *bs0 = mwoff + nm + 1, *bs1 = bs0 + nb;
-  uint32_t *ord = reinterpret_cast<uint32_t *>(bs1 + nb), *ohist = ord + ((nm + 1) & ~1u);
+  uint64_t *mwords, *mbeg, *mwoff, *bs0, *bs1;
+  uint32_t *ord, *ohist;
+  if (int rc = carve_reserve(ctx->status, 1024, [&](Carve &c) {
+        mwords = c.take(nm);  // the messages' words, then their streams' ends
+        mbeg = c.take(nm);
+        mwoff = c.take((uint64_t)nm + 1);
+        bs0 = c.take(scan_blocks(nm));  // the two scans' block sums
+        bs1 = c.take(scan_blocks(nm));
+        ord = c.take32(nm);  // the streams largest first
+        ohist = c.take32(cpk::kOrdClasses);
+      }))
+    return rc;
   const unsigned tb = 256, tg = (nm + tb - 1) / tb;
   // the segment counts go to d_msg_seg_off[0..nm) and are scanned into it
   // (e4_scan_down: each thread reads its entries before it writes them)
@@ -1296,9 +1339,8 @@ int cpk_decode_messages(cpk_ctx ctx, const void *d_packed, const uint64_t *d_msg
     const bool dense = ctx->decoder == 3 && pk[1] >= pk[0] && 100 * (pk[1] - pk[0]) >= 80 * 8 * h_totals[0];
     dec_launch(ctx, true, (nm + 3) / 4, (const uint8_t *)d_packed, d_seg_in_off, (const uint64_t *)d_seg_word_off,
                (uint32_t)h_totals[1], (uint64_t *)d_out, d_seg_status, 0,
-               cpk::DecStreams{mbeg, d_msg_off + 1, d_msg_seg_off, nm, mwords, nullptr,
-                               ord},
-               s, dense ? 3 : 0);
+               cpk::DecStreams::many(mbeg, d_msg_off + 1, d_msg_seg_off, nm, mwords, ord), s,
+               dense ? kDecDense : kDecCtx);
     hipLaunchKernelGGL(cpk::msg_final_kernel, dim3(tg), dim3(tb), 0, s, d_msg_off, nm,
                        (const uint64_t *)d_msg_seg_off, (const uint64_t *)mwords,
                        (const int32_t *)d_seg_status, d_msg_status);

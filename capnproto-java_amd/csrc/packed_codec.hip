@@ -61,9 +61,16 @@ constexpr int kTkErr = 17 * kTkStride;
 // bits of the error word (cpk_ctx_take_error): a piece over its size hint, a
 // timed-out cross-workgroup wait, packed bytes past the caller's capacity
 constexpr uint32_t kErrHint = 1u, kErrWait = 4u, kErrCap = 8u;
-constexpr int kTkGate = 17 * kTkStride + 8;  // [0..1] min, max piece words, [2] encoder choice, [3] sampled zero
-                                             // words, [6] single pass's form (1: sparse), [7] sampled words' packed
-                                             // bytes, [8..10] decoder choice
+// the gates' block (e4_minmax_kernel, e4_gate_kernel, sz_gate_kernel,
+// dec_gate_kernel) and its words
+constexpr int kTkGate = 17 * kTkStride + 8;
+constexpr int kGateMin = 0, kGateMax = 1;  // min, max piece words of the batch
+constexpr int kGatePick = 2;     // encoder / size form choice (nonzero: the single pass / the chunk form took it)
+constexpr int kGateZero = 3;     // sampled zero words
+constexpr int kGateSparse = 6;   // the single pass's form (1: sparse)
+constexpr int kGateBytes = 7;    // the sampled words' packed bytes
+constexpr int kGateDecSkip = 8;  // [3] decoder choice: nonzero = skip the block map, the record index, the dense
+                                 // block map
 constexpr int kTkWords = 18 * kTkStride;
 __device__ __forceinline__ int xcc_id() {
   int x;
@@ -780,6 +787,21 @@ struct DecStreams {
   uint64_t *send_out;
   const uint32_t *skip;   // (batch form: nonzero = the other decoder took the batch)
   const uint32_t *order;  // (stream form: ticket -> stream, largest first; null: in order)
+  // the forms the host passes: the batch form (skip: its gate word, or null)
+  static DecStreams batch(const uint32_t *skip = nullptr) {
+    return {nullptr, nullptr, nullptr, 0, nullptr, skip, nullptr};
+  }
+  // one stream, pieces 0..n-1, bytes [0, avail): its end to *end_out
+  static DecStreams one(uint64_t *end_out) { return {nullptr, nullptr, nullptr, 1, end_out, nullptr, nullptr}; }
+  // one stream from a device descriptor: desc[0] its begin, [1] its end, [2..3] its pieces
+  static DecStreams one_desc(const uint64_t *desc, uint64_t *end_out) {
+    return {desc, desc + 1, desc + 2, 1, end_out, nullptr, nullptr};
+  }
+  // ns streams, a wave each, in `order`; their ends to end_out[0..ns)
+  static DecStreams many(const uint64_t *sbeg, const uint64_t *send, const uint64_t *spc, uint32_t ns,
+                         uint64_t *end_out, const uint32_t *order) {
+    return {sbeg, send, spc, ns, end_out, nullptr, order};
+  }
 };
 template <bool kStream, bool kSerial = false>
 __device__ __forceinline__ void decode_body(uint8_t *smem, const uint8_t *__restrict__ packed,
