@@ -28,5 +28,6 @@ def test_chunk_div_is_exact_for_window_positions(c):
 def test_longest_record_fits_the_check_reach():
     longest = 1 + 8 + 1 + 8 * 255  # 0xFF tag, word, count, 255 verbatim words
     assert longest == 2050
-    k_win = 64 * 56
+    from _packed_records import kDecChunk  # parsed from csrc/packed_codec.hip
+    k_win = 64 * kDecChunk
     assert k_win + 2064 >= k_win + longest  # CPK_DEC_CHK_REACH default
