@@ -49,6 +49,23 @@ def test_assert_packs_to_kats(ctx, oracle):
     _check_batch(ctx, oracle, data, _swo([len(d) // 8 for d in datas]))
 
 
+def test_assert_packs_to_kats_batch_kernels(ctx, oracle, monkeypatch):
+    """The same vectors with CPK_NO_SMALL set.  Without it every host batch
+    this small goes to the one-workgroup kernel (small_ok(), host_pipe.hip)
+    whatever encoder the context forces, so the test above never reaches the
+    two-pass or the single-pass batch kernels its ids name; here each vector,
+    and all of them as one batch, go through cpk_encode_batch."""
+    monkeypatch.setenv("CPK_NO_SMALL", "1")
+    datas = []
+    for k in GOLD["kats"]:
+        u, p = bytes.fromhex(k["unpacked"]), bytes.fromhex(k["packed"])
+        pk, off = ctx.encode_host(np.frombuffer(u, dtype=np.uint8), _swo([len(u) // 8]))
+        assert pk.tobytes() == p and off.tolist() == [0, len(p)], k["source"]
+        datas.append(u)
+    data = np.frombuffer(b"".join(datas), dtype=np.uint8)
+    _check_batch(ctx, oracle, data, _swo([len(d) // 8 for d in datas]))
+
+
 def _random_words(rng, n, probs):
     kind = rng.choice(4, size=n, p=probs)
     w = rng.integers(1, 256, size=(n, 8), dtype=np.uint8)
@@ -388,6 +405,12 @@ def test_short_stretch_after_long(ctx, oracle):
     """A short D/L stretch whose 0xFF head lies within 255 words of a long
     stretch's last head: the head is not a member of the other stretch's run
     (PackedOutputStream.java:133-161 scan is per stretch)."""
+    pieces = _short_after_long_pieces()
+    data = np.concatenate(pieces)
+    _check_batch(ctx, oracle, data, _swo([len(p) // 8 for p in pieces]))
+
+
+def _short_after_long_pieces():
     pieces = []
     for sep in ([Z8], [np.array([1, 0, 0, 2, 0, 3, 0, 0], np.uint8)]):
         for gap in (0, 5, 100, 250):
@@ -395,8 +418,29 @@ def test_short_stretch_after_long(ctx, oracle):
             pieces.append(np.concatenate(p))
             p = [L8] * 10 + [D8] * 700 + sep + [L8] * gap + [D8] * 3
             pieces.append(np.concatenate(p))
+    return pieces
+
+
+def test_short_stretch_after_long_batch_kernels(ctx, oracle, monkeypatch):
+    """The same pieces past small_ok() (CPK_NO_SMALL): 8,000 words in 16
+    pieces otherwise go to the one-workgroup kernel under every ctx; here the
+    two-pass context runs e4_size_kernel / e4_emit_kernel on them, host and
+    device-resident."""
+    import torch
+    import capnp_packed as cp
+    monkeypatch.setenv("CPK_NO_SMALL", "1")
+    pieces = _short_after_long_pieces()
     data = np.concatenate(pieces)
-    _check_batch(ctx, oracle, data, _swo([len(p) // 8 for p in pieces]))
+    swo = _swo([len(p) // 8 for p in pieces])
+    pk, off = _check_batch(ctx, oracle, data, swo)
+    d_swo = torch.from_numpy(swo.astype(np.int64)).cuda()
+    d_in = torch.from_numpy(np.concatenate([data, np.zeros(8, np.uint8)]).view(np.int64).copy()).cuda()
+    d_pk = torch.zeros(batch_capacity_16(swo), dtype=torch.uint8, device="cuda")
+    d_off = torch.zeros(len(pieces) + 1, dtype=torch.int64, device="cuda")
+    ctx.encode_batch(d_in, d_swo, int(np.diff(swo.astype(np.int64)).max()), d_pk, d_off)
+    assert ctx.take_error() == cp.OK
+    assert np.array_equal(d_off.cpu().numpy().astype(np.uint64), off)
+    assert np.array_equal(d_pk[: int(off[-1])].cpu().numpy(), pk)
 
 
 @pytest.mark.parametrize("enc", ["default", "0", "4"])
