@@ -1128,10 +1128,42 @@ __device__ int serial_read(const uint8_t *p, uint64_t n, uint64_t &ip, uint32_t 
 struct NoWords {
   __device__ void operator()(uint32_t, uint64_t) const {}
 };
+// A valid table with a segment over 2^28 - 1 words: Serialize.read allocates
+// and reads the segments in order (:165-175) and makeByteBufferForWords
+// (:45-53) throws only when it reaches that segment, so a segment before it
+// that fails wins.  The table at tp is read again, each earlier segment
+// walked from sp[ip..sn) as its own read(), nothing stored.  -> the first
+// failure among them, else CPK_EFRAME.  (Malformed messages only.)
+__device__ int oversized_status(const uint8_t *tp, uint64_t tn, const uint8_t *sp, uint64_t sn, uint64_t ip,
+                                uint32_t count) {
+  int st = CPK_OK;
+  bool hit = false;
+  auto seg = [&](uint32_t sz) {
+    if (hit || st != CPK_OK) return;
+    if (sz > (uint32_t)kMaxSegmentWords)
+      hit = true;
+    else
+      st = serial_read(sp, sn, ip, sz, NoWords());
+  };
+  uint64_t tip = 0;
+  serial_read(tp, tn, tip, 1, [&](uint32_t, uint64_t w) { seg((uint32_t)(w >> 32)); });
+  if (count > 1) {
+    const uint32_t c = count;
+    serial_read(tp, tn, tip, (count & ~1u) / 2, [&](uint32_t i, uint64_t w) {
+      for (uint32_t h = 0; h < 2; ++h)
+        if (2 * i + h + 1 < c) seg((uint32_t)(w >> (32 * h)));
+    });
+  }
+  return st != CPK_OK ? st : CPK_EFRAME;
+}
+
 // (word(i, w): the table's words as read, i = 0 the first)
+// (sp, sn: the bytes the segments are walked in when one is oversized, the
+// table's end at the same offset as in p; null: p itself holds them)
 template <class F, class G = NoWords>
 __device__ int read_table(const uint8_t *p, uint64_t n, uint64_t limit, uint64_t &ip,
-                          uint32_t &count, uint64_t &total, F emit, G word = G()) {
+                          uint32_t &count, uint64_t &total, F emit, G word = G(),
+                          const uint8_t *sp = nullptr, uint64_t sn = 0) {
   uint64_t first = 0;
   int st = serial_read(p, n, ip, 1, [&](uint32_t, uint64_t w) {
     first = w;
@@ -1166,8 +1198,9 @@ __device__ int read_table(const uint8_t *p, uint64_t n, uint64_t limit, uint64_t
   }
   if (total > limit) return CPK_EFRAME;  // :160-162
   // makeByteBufferForWords (:45-53) throws for a segment over 2^28 - 1 words
-  // when that segment is allocated: the message fails either way
-  if (big) return CPK_EFRAME;
+  // when that segment is allocated, in segment order: the message fails
+  // either way, with an earlier segment's failure if one fails
+  if (big) return oversized_status(p, n, sp ? sp : p, sp ? sn : n, ip, count);
   return CPK_OK;
 }
 
@@ -1314,8 +1347,8 @@ struct RmScratch {
   uint64_t fill[2];    // swo padding: first index, value
 };
 static_assert(kRmTableBytes % 16 == 0 && kRmTableBytes + sizeof(RmScratch) <= kDecLds, "rm_small_kernel LDS");
-__device__ void rm_table_parse(const uint8_t *tb, uint64_t nt, uint64_t avail, uint64_t limit, uint64_t cap_words,
-                               uint64_t *__restrict__ swo, uint64_t *__restrict__ info,
+__device__ void rm_table_parse(const uint8_t *tb, uint64_t nt, const uint8_t *packed, uint64_t avail, uint64_t limit,
+                               uint64_t cap_words, uint64_t *__restrict__ swo, uint64_t *__restrict__ info,
                                uint64_t *__restrict__ sdesc, uint64_t *__restrict__ out, RmScratch &rs);
 __device__ __forceinline__ void rm_table_body(const uint8_t *__restrict__ packed, uint64_t avail, uint64_t limit,
                                               uint64_t cap_words, uint64_t *__restrict__ swo,
@@ -1332,7 +1365,7 @@ __device__ __forceinline__ void rm_table_body(const uint8_t *__restrict__ packed
   for (uint32_t i = threadIdx.x; i < (uint32_t)((nt + 15) / 16); i += blockDim.x)
     reinterpret_cast<uint4 *>(tb)[i] = reinterpret_cast<const uint4 *>(packed)[i];
   __syncthreads();
-  if (threadIdx.x == 0) rm_table_parse(tb, nt, avail, limit, cap_words, swo, info, sdesc, out, rs);
+  if (threadIdx.x == 0) rm_table_parse(tb, nt, packed, avail, limit, cap_words, swo, info, sdesc, out, rs);
   if (out) return;
   __syncthreads();
   const uint32_t f0 = (uint32_t)rs.fill[0];
@@ -1348,17 +1381,27 @@ __global__ void rm_table_kernel(const uint8_t *__restrict__ packed, uint64_t ava
 }
 // (one thread) the table read and checked as doRead does, the message laid
 // out as the stream's pieces
-__device__ void rm_table_parse(const uint8_t *tb, uint64_t nt, uint64_t avail, uint64_t limit, uint64_t cap_words,
-                               uint64_t *__restrict__ swo, uint64_t *__restrict__ info,
+__device__ void rm_table_parse(const uint8_t *tb, uint64_t nt, const uint8_t *packed, uint64_t avail, uint64_t limit,
+                               uint64_t cap_words, uint64_t *__restrict__ swo, uint64_t *__restrict__ info,
                                uint64_t *__restrict__ sdesc, uint64_t *__restrict__ out, RmScratch &rs) {
   uint64_t ip = 0, total = 0;
   uint32_t count = 0;
+  // (an oversized segment: the segments before it are walked in the bytes the
+  // call may read, 10 per word of the caller's capacity, ss_reach)
+  const uint64_t room = cap_words > (~0ull - 16) / 10 - kRmHead ? ~0ull : 10 * (cap_words + kRmHead) + 16;
+  const uint64_t sn = min(avail, room);
   int st = read_table(
       tb, nt, limit, ip, count, total, [&](uint32_t i, uint32_t sz) { rs.size[i] = sz; },
       [&](uint32_t i, uint64_t w) {
         if (out) out[i] = w;
-      });
+      },
+      packed, sn);
   if (st == CPK_OK && total > cap_words) st = CPK_ENOMEM;
+  // (a table always ends within kRmTableBytes < room, so with room's bytes
+  // at hand only that walk can come up short: the segments before the
+  // oversized one exceed the capacity, and where they end is not known --
+  // the table's own verdict stands)
+  if (st == CPK_ETRUNC && sn == room) st = CPK_EFRAME;
   info[0] = (uint64_t)(int64_t)st;
   info[1] = 0;
   info[2] = st == CPK_OK || st == CPK_ENOMEM ? count : 0;

@@ -51,6 +51,13 @@ extern "C" {
  *   CPK_EFRAME    segment table invalid: count over 512, a negative size, a
  *                 message over the traversal limit or a segment over 2^28-1
  *                 words -> DecodeException (Serialize.java:45-53, :125-163).
+ *                 The last is thrown in segment order, when the read reaches
+ *                 that segment (:165-175): a segment before it that fails
+ *                 gives the message its own status (CPK_ETRUNC,
+ *                 CPK_EOVERRUN) instead.  Such a message reports its status
+ *                 at any capacity, never CPK_ENOMEM; cpk_read_message walks
+ *                 the earlier segments in the bytes it may read and reports
+ *                 CPK_EFRAME when they end beyond those.
  *   CPK_ENOMEM, CPK_EDEVICE  allocation / HIP runtime failure (-> IOException).
  *   CPK_EUNSUPPORTED  a piece outside what this build handles.
  */

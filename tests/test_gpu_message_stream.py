@@ -49,11 +49,12 @@ def _write_pieces(oracle, msg, first_word=None):
     return out + b"".join(oracle.pack(s) for s in msg)
 
 
-def _oracle_loop(oracle, data, limit=LIMIT):
-    """while (...) SerializePacked.read(in) -> (messages, their first bytes + the end, tail status)."""
+def _oracle_loop(oracle, data, limit=LIMIT, out_cap=2 * 1024 * 1024):
+    """while (...) SerializePacked.read(in) -> (messages, their first bytes + the end, tail status).
+    (out_cap: the oracle's output bytes per message; more for a stream that declares a huge segment)"""
     msgs, offs, pos, st = [], [0], 0, oracle.OK
     while pos < len(data):
-        st, segs, used = oracle.read_message(data[pos:], limit, out_cap=2 * 1024 * 1024)
+        st, segs, used = oracle.read_message(data[pos:], limit, out_cap=out_cap)
         if st != oracle.OK:
             break
         msgs.append(segs)
@@ -221,9 +222,9 @@ def _decode(ctx, data, limit=LIMIT):
     return info, msgs, [int(v) for v in mo[:info[0] + 1]]
 
 
-def _compare(ctx, oracle, data, limit=LIMIT):
+def _compare(ctx, oracle, data, limit=LIMIT, out_cap=2 * 1024 * 1024):
     import capnp_packed as cp
-    want, offs, st = _oracle_loop(oracle, data, limit)
+    want, offs, st = _oracle_loop(oracle, data, limit, out_cap)
     info, msgs, mo = _decode(ctx, data, limit)
     print("info", info, "oracle", len(want), sum(len(m) for m in want), offs[-1], st)
     assert info[4] != cp.EUNSUPPORTED
