@@ -2,7 +2,8 @@
 // workgroup: the one-launch path of cpk_read_message_host for messages up to
 // kRmMwMax bytes (Serialize.read's pieces one after another, each piece's
 // windows spread over the waves).  Included from packed_codec.hip (namespace
-// cpk) after rm_small_kernel.
+// cpk) after rm_small_kernel; the window load and the walks are
+// decode_win.hip's, win_emit decode_map.hip's.
 //
 // decode_body starts each window at a known tag position (the previous
 // window's exit), so one wave walks a piece window by window and a lone wave's
@@ -56,10 +57,6 @@ __device__ __forceinline__ uint32_t mw_get(uint64_t *slot, uint32_t tag, uint32_
   }
   return (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
 }
-__device__ __forceinline__ uint64_t mw_rl64(uint64_t v, int l) {
-  return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l) |
-         ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32);
-}
 
 // One wave's window t (grid start g) of the piece at packed offset a
 // (P readable bytes of the stream from there, W words into dst).  Returns
@@ -77,33 +74,14 @@ __device__ __forceinline__ bool mw_window(uint8_t *wl, const uint64_t *lut, MwSh
   const uint32_t wend = live ? min(g + kWin, P) : 0u;
   const uint8_t *pkw = wbuf;
   uint32_t lend = 0, ph = 0;
-  WinWalk ww = {0u, 0u, 0u, 0u, 0ull};
+  WinWalk ww = {0u, 0u, 0u, 0u, 0ull, 0u, 0u};
 #ifdef CPK_PHASE_STATS
   unsigned long long wph_last = 0, wph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
   if (live) {
-    // the window's bytes (as decode_body loads them)
-    const uint32_t padw = (uint32_t)((a + g) & 15);
-    const uint32_t ebase = g - padw;
-    const uint32_t need = min(g + kWin + kDecLook, P) - ebase;
-    const uint32_t lines = (need + 15) >> 4;
-    const uint4 *gsrc = reinterpret_cast<const uint4 *>(gp - padw + g);
-    uint4 l[kWinLinesPerLane];
-#pragma unroll
-    for (int j = 0; j < kWinLinesPerLane; ++j) {
-      const uint32_t L = lane + 64 * j;
-      l[j] = L < lines ? gsrc[L] : make_uint4(0u, 0u, 0u, 0u);
-    }
-#pragma unroll
-    for (int j = 0; j < kWinLinesPerLane; ++j) {
-      const uint32_t L = lane + 64 * j;
-      if (L < lines) reinterpret_cast<uint4 *>(wbuf)[L] = l[j];
-    }
-    lend = ebase + 16 * lines;
-    pkw = wbuf + (int64_t)padw - (int64_t)g;
-    ph = (padw - g) & 3;
-    wave_lds_order();
-    ww = win_walks<false>(pkw, visa, lane, g, wend DEC_PH_ARGS);
+    const WinBytes wb = win_load<DecGeom>(wbuf, lane, gp, a, g, P);
+    pkw = wb.pkw, lend = wb.lend, ph = wb.ph;
+    ww = win_walks<false, DecGeom>(pkw, visa, lane, g, wend DEC_PH_ARGS);
   }
   // ---- the entry (serial over the windows) ----------------------------------
   const uint32_t ein = mw_get(&ms.E[slot], t, &ms.tmo);
@@ -132,8 +110,8 @@ __device__ __forceinline__ bool mw_window(uint8_t *wl, const uint64_t *lut, MwSh
     q = (uint32_t)readlane((int)q, j);
     o = readlane(o, j);
     sw = (uint32_t)readlane((int)sw, j);
-    if (o == j) onmask = mw_rl64(ww.R, j);  // into lane j's own walk
-    else if (o > j) onmask = (1ull << j) | mw_rl64(ww.R, o);
+    if (o == j) onmask = readlane64(ww.R, j);  // into lane j's own walk
+    else if (o > j) onmask = (1ull << j) | readlane64(ww.R, o);
     else onmask = 1ull << j;                // out of the window
     if (lane == j && o != j) S = q;
     enext = (uint32_t)readlane((int)S, 63 - __builtin_clzll(onmask));

@@ -1,7 +1,8 @@
 // decode_v2.hip -- the decoder with a record index (the default).  Included
-// from packed_codec.hip (namespace cpk): the window load, the speculative
-// chunk walks and the pointer-doubling chain resolution are decode_kernel's;
-// what follows differs.
+// from packed_codec.hip (namespace cpk): the pieces, the window load, the
+// speculative chunk walks and the pointer-doubling chain resolution are
+// decode_win.hip's, shared with decode_kernel (decode_map.hip); what follows
+// differs.
 //
 // decode_kernel maps every 4-word output block to its covering record by
 // walking each true record once per expansion round and writing one map entry
@@ -27,22 +28,18 @@ constexpr int kD2Threads = 256;  // 4 independent waves
 // workgroups per CU the register budget is sized for (LDS allows 5)
 constexpr int kD2Wpe = 5;
 constexpr uint32_t kD2Chunk = 48;
-constexpr uint32_t kD2Win = 64 * kD2Chunk;                           // packed bytes per window
-constexpr uint32_t kD2WinBuf = (kD2Win + 15 + 32 + 16 + 15) & ~15u;  // + pad, look-ahead, slack
+constexpr uint32_t kD2Look = 32;  // bytes loaded past the window
+typedef WinGeom<kD2Chunk, kD2Look> D2Geom;
+constexpr uint32_t kD2Win = D2Geom::win, kD2WinBuf = D2Geom::buf, kD2ChkReach = D2Geom::reach;
 constexpr uint32_t kD2NI = 1024;  // records indexed per window
 constexpr uint32_t kD2Round = 2048;  // output words per expansion round
 constexpr int kD2Unroll = 4;  // 64-word groups expanded together
-typedef std::conditional<(kD2Chunk <= 32), uint32_t, uint64_t>::type D2Vis;
-static_assert(kD2Chunk <= 64, "visited mask bits");
 constexpr uint32_t kD2Info = kD2NI * 4;
-static_assert(kD2Info >= 64 * sizeof(D2Vis) + 8, "visited masks live over the index");
-// record starts of a round: a byte per output word (plain byte stores, one
-// per record: consecutive records never contend for one LDS address as bits
-// OR-ed into a shared word would), or a bit per word with atomics
-constexpr uint32_t kD2Bits = 0 ? kD2Round : kD2Round / 8;
+static_assert(kD2Info >= 64 * sizeof(VisMask) + 8, "visited masks live over the index");
+// record starts of a round: a bit per output word, set with atomics
+constexpr uint32_t kD2Bits = kD2Round / 8;
 constexpr uint32_t kD2WaveLds = kD2WinBuf + kD2Info + kD2Bits;
 constexpr uint32_t kD2Lds = 2048 + 4 * kD2WaveLds;
-constexpr int kD2LinesPerLane = (int)((kD2Win + 47 + 15) / 16 + 63) / 64;
 static_assert(kD2Win <= 4095, "record positions are 12-bit");
 
 template <bool kStream>
@@ -57,73 +54,22 @@ __global__ __launch_bounds__(kD2Threads, kD2Wpe) void decode2_kernel(
   uint8_t *wbuf = wl;                                            // window bytes
   uint32_t *info = reinterpret_cast<uint32_t *>(wl + kD2WinBuf); // [kD2NI] record index
   uint32_t *bits = reinterpret_cast<uint32_t *>(wl + kD2WinBuf + kD2Info);  // record starts of a round
-  D2Vis *visa = reinterpret_cast<D2Vis *>(info);  // [64], over the index (phases 1-3)
+  VisMask *visa = reinterpret_cast<VisMask *>(info);  // [64], over the index (phases 1-3)
   if (sd.skip && __builtin_amdgcn_readfirstlane(*sd.skip)) return;
   fill_luts(lut, true);
   __syncthreads();  // the only block-wide barrier: LUT ready
-  int xq = xcc_id(), dry = 0;
+  DecPieces<kStream> pc(swo, in_off, status, ticket, n, avail, sd);
   WPH_INIT
-  uint64_t scur = 0;      // stream mode: start of the next piece
-  uint64_t slim = avail;  //   end of the stream's bytes
-  int sfail = CPK_OK;     //   a failed piece stops the stream
-  uint32_t snext = 0, sende = 0, sj = 0;  // next piece, end of the stream's pieces, stream
 
-  for (uint32_t sidx = 0;; ++sidx) {
-    // every branch below is on wave-uniform (SGPR) values: the compiler
-    // must not turn the piece / window loops into divergent loops
-    // All 64 lanes add 1 (hipcc folds it into one +64 atomic): no lane-0-only
-    // branch at the loop head, which hipcc otherwise structurised into a
-    // divergent loop re-running piece 0.  Tickets count in units of 64.
-    uint32_t seg = sidx;
-    if (!kStream) {
-      for (;;) {
-        seg = take_ticket(ticket, xq);
-        if (seg < n || ++dry >= 8) break;
-        xq = (xq + 1) & 7;  // this counter ran dry: help the next one
-      }
-    } else {
-      // the next stream with pieces (empty streams end where they begin)
-      bool more = true;
-      while (snext >= sende) {
-        uint32_t j;
-        for (;;) {
-          j = take_ticket(ticket, xq);
-          if (j < sd.ns || ++dry >= 8) break;
-          xq = (xq + 1) & 7;
-        }
-        if (j >= sd.ns) {
-          more = false;
-          break;
-        }
-        sj = j;
-        snext = sd.sbeg ? (uint32_t)sd.spc[j] : 0u;
-        sende = sd.sbeg ? (uint32_t)sd.spc[j + 1] : n;
-        scur = sd.sbeg ? sd.sbeg[j] : 0;
-        slim = sd.sbeg ? sd.send[j] : avail;
-        sfail = CPK_OK;
-        if (snext >= sende) sd.send_out[j] = scur;
-      }
-      if (!more) break;
-      seg = snext++;
-    }
-    if (seg >= n) break;
-    const uint64_t w0 = swo[seg];
-    const int W = (int)(swo[seg + 1] - w0);
-    const uint64_t a = kStream ? scur : in_off[seg];
-    const uint32_t P = kStream ? (uint32_t)min(slim - scur, (uint64_t)0xffffffffu)
-                               : (uint32_t)(in_off[seg + 1] - a);
-    if (kStream && sfail != CPK_OK) {
-      status[seg] = sfail;
-      if (seg + 1 == sende) sd.send_out[sj] = scur;
-      continue;
-    }
+  while (pc.next()) {
+    const int W = pc.W;
+    const uint64_t a = pc.a;
+    const uint32_t P = pc.P, glim = pc.glim;
     const uint8_t *gp = packed + a;
-    const uint32_t glim = (uint32_t)(((a + P + 15) & ~15ull) - a);  // readable bytes
-    uint64_t *dst = out + w0;
-    int st = CPK_OK;
+    uint64_t *dst = out + pc.w0;
+    int st = W == 0 ? pc.empty_status() : CPK_OK;
     uint32_t e = 0;  // true tag position (piece-relative)
     int ow = 0;      // output words produced
-    if (W == 0) st = (P == 0 || kStream) ? CPK_OK : CPK_ETRAILING;  // read() of 0 bytes
     while (W != 0) {
       e = (uint32_t)__builtin_amdgcn_readfirstlane((int)e);  // (wave-uniform: SGPRs, scalar branches)
       ow = __builtin_amdgcn_readfirstlane(ow);
@@ -134,126 +80,21 @@ __global__ __launch_bounds__(kD2Threads, kD2Wpe) void decode2_kernel(
       if (ow >= W) break;  // (trailing input is flagged by the record check)
       const uint32_t wend = min(e + kD2Win, P);
       WPH(0)
-      // ---- window load: LDS byte x <-> packed[(a + e) & ~15 + x] ----------
-      const uint32_t padw = (uint32_t)((a + e) & 15);
-      const uint32_t ebase = e - padw;  // piece position of wbuf[0]
-      const uint32_t need = min(e + kD2Win + 32, P) - ebase;  // <= kD2Win + 47 bytes
-      const uint32_t lines = (need + 15) >> 4;
-      const uint4 *gsrc = reinterpret_cast<const uint4 *>(gp - padw + e);
-      // all of a lane's lines (<= 3) in flight at once, then the LDS writes:
-      // one memory latency per window instead of one per line
-      {
-        uint4 l[kD2LinesPerLane];
-#pragma unroll
-        for (int j = 0; j < kD2LinesPerLane; ++j) {
-          const uint32_t L = lane + 64 * j;
-          l[j] = L < lines ? gsrc[L] : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int j = 0; j < kD2LinesPerLane; ++j) {
-          const uint32_t L = lane + 64 * j;
-          if (L < lines) reinterpret_cast<uint4 *>(wbuf)[L] = l[j];
-        }
-      }
-      const uint32_t lend = ebase + 16 * lines;  // loaded piece positions < lend
-      // pkw[q] = packed byte q (signed 64-bit offset: ebase is negative when
-      // the piece starts mid-line)
-      const uint8_t *pkw = wbuf + (int64_t)padw - (int64_t)e;
-      const uint32_t ph = (padw - e) & 3;  // LDS byte phase of piece position 0
-      wave_lds_order();
+      const WinBytes wb = win_load<D2Geom>(wbuf, lane, gp, a, e, P);
+      const uint8_t *pkw = wb.pkw;
+      const uint32_t lend = wb.lend, ph = wb.ph;
 
       WPH(1)
-      // ---- 1: speculative chunk walks --------------------------------------
-      const uint32_t cb = e + kD2Chunk * lane;
-      const uint32_t ce = min(cb + kD2Chunk, wend);
-      D2Vis vis = 0;
-      uint32_t X = cb, wt = 0;  // wt: output words of the walk
-      if (cb < wend) {
-        uint32_t pos = cb;
-        while (pos < ce) {
-          vis |= (D2Vis)1 << (pos - cb);
-          const DecRec r = rec_at<!kStream>(pkw, pos);
-          wt += r.nw;
-          pos += r.len;
-        }
-        X = pos;
-      }
-      visa[lane] = vis;
-      wave_lds_order();
-      // ---- 2: walk on until landing on a visited position -------------------
-      uint32_t S = X, lw = 0, lr = 0;  // lw / lr: output words / records of the landing walk
-      if (cb < wend) {
-        while (S < wend) {
-          const uint32_t r = S - e;
-          const uint32_t ow_ = r / kD2Chunk;
-          if ((visa[ow_] >> (r - ow_ * kD2Chunk)) & 1) break;
-          const DecRec rr = rec_at<!kStream>(pkw, S);
-          lw += rr.nw;
-          ++lr;
-          S += rr.len;
-        }
-      }
-      WPH(2)
-      // ---- 3: true chain over lanes -----------------------------------------
-      // lane j's successor is the owner of its landing point (always a later
-      // lane); the true records are on the lanes reachable from lane 0, found
-      // by pointer doubling (6 rounds cover a chain of 64)
-      int nx = (cb < wend && S < wend) ? (int)((S - e) / kD2Chunk) : 64;
-      uint64_t R = 1ull << lane;
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        const int src = (nx & 63) << 2;
-        const uint32_t rlo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)R);
-        const uint32_t rhi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)(R >> 32));
-        const int nn = __builtin_amdgcn_ds_bpermute(src, nx);
-        if (nx < 64) {
-          R |= ((uint64_t)rhi << 32) | rlo;
-          nx = nn;
-        }
-      }
-      const uint64_t onmask = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)R, 0)) |
-                              ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(R >> 32), 0) << 32);
-      const uint32_t enext =
-          (uint32_t)__builtin_amdgcn_readlane((int)S, 63 - __builtin_clzll(onmask));
-      // each on-path lane hands its landing point to its successor
-      wave_lds_order();  // (phase 2's reads of visa are done)
-      if (((onmask >> lane) & 1) && S < wend) visa[(S - e) / kD2Chunk] = (D2Vis)S;
-      wave_lds_order();
-      const uint32_t entry = lane == 0 ? e : (uint32_t)visa[lane];
-      const bool on = (onmask >> lane) & 1;
-      WPH(3)
-      // ---- 4: output words of each lane's true records ----------------------
-      // [entry, S) = the walk's records from entry (a position the walk
-      // visited) plus the landing walk: the walk's words minus those before
-      // entry (usually one or two records of a false start)
-      // ... and its true records: the walk's visited positions from entry on
-      // plus the landing walk's
-      int myw = 0, myr = 0;
-      if (on) {
-        uint32_t pre = 0;
-        for (uint32_t q = cb; q < entry;) {
-          const DecRec r = rec_at<!kStream>(pkw, q);
-          pre += r.nw;
-          q += r.len;
-        }
-        myw = (int)(wt - pre + lw);
-        const uint32_t eb = entry - cb;  // (< kD2Chunk: entry is a visited position)
-        myr = __builtin_popcountll((uint64_t)vis) - __builtin_popcountll((uint64_t)vis & ((1ull << eb) - 1)) +
-              (int)lr;
-      }
-      const int inc = wave_incl_add(myw);
-      const int T = readlane(inc, 63);
-      const int o0 = inc - myw;  // window-relative output of this lane's first record
-      const int incr = wave_incl_add(myr);
-      const int NR = readlane(incr, 63);  // true records in the window
-      const int r0 = incr - myr;          // rank of this lane's first record
-      WPH(4)
+      // ---- 1-4: the walks, the true chain, each lane's words and records -----
+      const WinWalk ww = win_walks<!kStream, D2Geom, true>(pkw, visa, lane, e, wend DEC_PH_ARGS);
+      const WinChain wc = win_chain<!kStream, D2Geom, true>(pkw, visa, lane, e, wend, ww DEC_PH_ARGS);
+      const uint32_t S = ww.S, entry = wc.entry, enext = wc.enext;
+      const bool on = wc.on;
+      const int T = wc.T, o0 = wc.o0, NR = wc.NR, r0 = wc.r0;
       // ---- 5: the index: each true record's window position and first word ----
       // (the reference's error checks run in a window that may reach the
       // piece's end: PackedInputStream.java:53-138)
-      // (within one window plus the longest record, 2,050 bytes, of the end:
-      // the window's records start before e + kD2Win)
-      const bool chk = (ow + T >= W) || (P - e < kD2Win + 2064);
+      const bool chk = (ow + T >= W) || (P - e < kD2ChkReach);
       // a window with more true records than the index holds ends at its
       // kD2NI-th record (scr: that record's position and first word)
       const bool cut = NR > (int)kD2NI;
@@ -396,13 +237,7 @@ __global__ __launch_bounds__(kD2Threads, kD2Wpe) void decode2_kernel(
       ow += (int)Teff;
       e = eff_next;
     }
-    status[seg] = st;  // every lane the same value: no lane-dependent branch
-    if (kStream) {
-      in_off[seg] = a;
-      scur = a + e;
-      sfail = st;
-      if (seg + 1 == sende) sd.send_out[sj] = scur;
-    }
+    pc.done(st, e);
   }
   WPH_FLUSH(16)
 }

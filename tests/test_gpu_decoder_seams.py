@@ -3,7 +3,7 @@ decoders' own geometry, through every decoder form, against the oracle bit
 for bit (tests/_packed_records.py builds the corpora; tests/
 test_packed_records.py pins them on the CPU and checks their coverage).
 
-  block map / dense   packed_codec.hip   windows of kWin packed bytes, lane
+  block map / dense   decode_map.hip     windows of kWin packed bytes, lane
                                          chunks, the kDecLook look-ahead, rounds
                                          of kRound words, kBlk-word blocks, the
                                          check reach, the serial walk's cap
