@@ -42,6 +42,7 @@ EXPORTS = [
     "cpk_encode_message_stream", "cpk_encode_message_stream_host",
     "cpk_packed_size_batch", "cpk_packed_size_messages", "cpk_packed_size_host",
     "cpk_packed_size_messages_host",
+    "cpk_unpacked_size_batch", "cpk_unpacked_size_host",
 ]
 MSG_HEAD_WORDS, MSG_INFO_WORDS = 257, 517  # CPK_MSG_HEAD_WORDS, CPK_MSG_INFO_WORDS
 MS_INFO_WORDS = 5  # CPK_MS_INFO_WORDS
@@ -121,6 +122,8 @@ def load(path: Path | None = None, strict: bool = True) -> ctypes.CDLL:
         "cpk_packed_size_messages": ([vp, vp, vp, u32, vp, u32, u64, vp, vp], i32),
         "cpk_packed_size_host": ([vp, vp, vp, u32, vp], i32),
         "cpk_packed_size_messages_host": ([vp, vp, vp, u32, vp, u32, vp], i32),
+        "cpk_unpacked_size_batch": ([vp, vp, vp, u32, vp, vp, vp], i32),
+        "cpk_unpacked_size_host": ([vp, vp, vp, u32, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         if not strict and not hasattr(L, name):
@@ -670,7 +673,38 @@ def _packed_size_messages_host(self, messages) -> np.ndarray:
     return off
 
 
+def _unpacked_size_batch(self, d_packed, d_in_off, d_seg_word_off, d_status, stream=None):
+    """cpk_unpacked_size_batch: d_seg_word_off[n+1] gets the word offsets
+    decode_batch must be given for the packed ranges d_in_off[n+1] -- no word
+    is decoded; d_seg_word_off[n] is the total.  d_status[n]: OK, or ETRUNC
+    for a range that ends inside a record (it sizes to 0 words).  A batch of
+    at most 32 pieces synchronises `stream` once, as decode_batch does."""
+    n = d_in_off.numel() - 1
+    rc = self._lib.cpk_unpacked_size_batch(self.handle, d_packed.data_ptr(), d_in_off.data_ptr(), n,
+                                           d_seg_word_off.data_ptr(), d_status.data_ptr() if n else None,
+                                           self._stream(stream))
+    _check(rc, "cpk_unpacked_size_batch")
+
+
+def _unpacked_size_host(self, packed: np.ndarray, in_off: np.ndarray):
+    """cpk_unpacked_size_host -> (seg_word_off uint64[n+1], status int32[n]):
+    what decode_host needs besides the packed ranges.  Never raises on bad
+    data: a truncated piece has status ETRUNC and 0 words."""
+    io = np.ascontiguousarray(in_off, dtype=np.uint64)
+    n = len(io) - 1
+    pk = np.ascontiguousarray(packed, dtype=np.uint8)
+    swo = np.zeros(n + 1, dtype=np.uint64)
+    st = np.zeros(max(n, 1), dtype=np.int32)
+    rc = self._lib.cpk_unpacked_size_host(self.handle, pk.ctypes.data if pk.size else None, io.ctypes.data, n,
+                                          swo.ctypes.data, st.ctypes.data)
+    if rc not in (OK, ETRUNC):
+        _check(rc, "cpk_unpacked_size_host")
+    return swo, st[:n]
+
+
 Context.packed_size_batch = _packed_size_batch
+Context.unpacked_size_batch = _unpacked_size_batch
+Context.unpacked_size_host = _unpacked_size_host
 Context.packed_size_messages = _packed_size_messages
 Context.packed_size_host = _packed_size_host
 Context.packed_size_messages_host = _packed_size_messages_host

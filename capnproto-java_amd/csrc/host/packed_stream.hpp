@@ -59,6 +59,19 @@ class Gpu {  // one device context, shared by the streams below
   cpk_ctx ctx_ = nullptr;
 };
 
+// The words `len` packed bytes unpack to, without unpacking them (upstream
+// Cap'n Proto's computeUnpackedSizeInWords, serialize-packed.h): what a
+// PackedInputStream.read of the whole range would be asked for.  Throws
+// DecodeException when the bytes end inside a record (cpk_unpacked_size_host
+// with one piece).
+inline uint64_t computeUnpackedSizeInWords(Gpu &gpu, const uint8_t *bytes, size_t len) {
+  const uint64_t in_off[2] = {0, len};
+  uint64_t swo[2] = {0, 0};
+  int32_t st = CPK_OK;
+  check(cpk_unpacked_size_host(gpu.get(), bytes, in_off, 1, swo, &st), "computeUnpackedSizeInWords");
+  return swo[1];
+}
+
 // ---- in-memory channels (ArrayOutputStream / ArrayInputStream) ----
 class ArrayOutputStream {
  public:

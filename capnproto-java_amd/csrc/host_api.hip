@@ -41,6 +41,7 @@ struct cpk_ctx_s {
   int e4_order;           // cpk_encode_messages' two passes, segments largest first: 1 both passes,
                           // 2 the emit pass only, 0 neither (CPK_E4_ORDER)
   int size_form;          // cpk_packed_size_batch: 0 by piece size, 1 chunk parallel, 2 wave per piece (CPK_SIZE_FORM)
+  int usize_form;         // cpk_unpacked_size_batch: 0 by piece size, 1 block map, 2 wave per piece (CPK_USIZE_FORM)
   // CPK_HOST_TRACE=1 (read at creation): host wall time of the one-message
   // host paths (cpk_encode_host[_gather], cpk_read_message_host) by phase,
   // summed per context and printed to stderr by cpk_ctx_destroy
@@ -190,6 +191,8 @@ int sizes_scratch(cpk_ctx ctx, uint32_t n, uint64_t *&sizes, uint64_t *&bsum) {
 
 static int decode_batch_impl(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off, const uint64_t *d_swo,
                              uint32_t n, void *d_out, int32_t *d_status, void *stream, bool probe);
+static int unpacked_size_impl(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off, uint32_t n,
+                              uint64_t *d_swo, int32_t *d_status, void *stream, bool probe, const uint64_t *h_off);
 
 // The end of a one-launch small path (rm_small_kernel, sp_small_kernel):
 // its kernel writes seq to *flag (pinned host memory) after all its other
@@ -297,6 +300,10 @@ int cpk_ctx_create(int device, cpk_ctx *out) {
     // CPK_SIZE_FORM=chunk / wave forces the size query's form (A/B of its gate)
     const char *z = getenv("CPK_SIZE_FORM");
     c->size_form = (z && z[0] == 'c') ? 1 : (z && z[0] == 'w') ? 2 : 0;
+    // CPK_USIZE_FORM=1 / 2 forces the unpacked-size query's form: the block
+    // map for every piece it can take, a wave per piece (A/B of its threshold)
+    const char *u = getenv("CPK_USIZE_FORM");
+    c->usize_form = (u && u[0] == '1') ? 1 : (u && u[0] == '2') ? 2 : 0;
   }
   if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
     c->cus = 256;
@@ -1113,6 +1120,103 @@ int cpk_decode_message_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
   h_info[3] = r[3];
   h_info[4] = r[4];
   return CPK_OK;
+}
+
+// ---- unpacked sizes without decoding (decode_size.hip) ---------------------
+// A wave per piece sums its windows' words into the context's workspace, the
+// size scan turns them into d_seg_word_off.  A few large pieces (n <= 32)
+// would each keep one wave busy for the whole call: where the host knows
+// their offsets (h_off, the host form) or may read them back (probe), a large
+// piece that starts on a 16-byte line is sized by the block map over its
+// bytes alone (ss_map_launch, us_end_kernel); what that cannot settle -- an
+// irregular map, a piece ending inside a record -- stays marked in todo and
+// the wave form sizes it after all.
+// One piece of config-2 data by both forms (tools/bench_unpacked_size.py,
+// profiles/unpacked_size_bench.log; DESIGN.md section 4 has the table): one
+// wave walks 1 MiB in 1.7 ms, the map's launches take 0.12 ms up to 512 KiB
+// and 0.75 ms at 256 MiB -- level at 64 KiB.  The maps of several pieces run
+// one after the other while their waves would run side by side, so a piece
+// of a batch of n takes the map from n * kUsBlockMin bytes.
+constexpr uint64_t kUsBlockMin = 64 * 1024;
+static int unpacked_size_impl(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off, uint32_t n,
+                              uint64_t *d_swo, int32_t *d_status, void *stream, bool probe, const uint64_t *h_off) {
+  using namespace cpk;
+  if (!ctx || !d_swo || (n && (!d_in_off || !d_status))) return CPK_EINVAL;
+  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_in_off & 7) || ((uintptr_t)d_swo & 7) || ((uintptr_t)d_status & 3))
+    return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) return hip_ok(hipMemsetAsync(d_swo, 0, 8, s));
+  // words [n] | the scan's block sums | todo [n] (u32)
+  uint64_t *words, *bsum;
+  uint32_t *todo;
+  if (int rc = carve_reserve(ctx->status, 1024, [&](Carve &c) {
+        words = c.take(n);
+        bsum = c.take(scan_blocks(n) + 1);
+        todo = c.take32(n);
+      }))
+    return rc;
+  const uint8_t *pk = (const uint8_t *)d_packed;
+  bool mapped = false;
+  if (n <= 32 && ctx->usize_form != 2 && (h_off || probe)) {
+    uint64_t off[33];
+    bool large = ctx->usize_form == 1;
+    if (h_off) {
+      memcpy(off, h_off, (n + 1) * 8ull);
+    } else {
+      uint64_t e[2];
+      if (int rc = read_words(ctx, s, {d_in_off, d_in_off + n}, e)) return rc;
+      off[0] = e[0];
+      off[n] = e[1];
+      large = large || (e[1] >= e[0] && e[1] - e[0] >= n * kUsBlockMin);
+      // the pieces in between (a second small read-back, only on this path)
+      if (large && n > 1 &&
+          (hipMemcpyAsync(off, d_in_off, (n + 1) * 8ull, hipMemcpyDeviceToHost, s) != hipSuccess ||
+           hipStreamSynchronize(s) != hipSuccess))
+        return CPK_EDEVICE;
+    }
+    auto takes = [&](uint32_t i) {
+      const uint64_t len = off[i + 1] - off[i];
+      return off[i + 1] > off[i] && (off[i] & 15) == 0 && (ctx->usize_form == 1 || len >= n * kUsBlockMin);
+    };
+    uint64_t nbmax = 0;
+    for (uint32_t i = 0; (large || h_off) && i < n; ++i)
+      if (takes(i)) nbmax = max(nbmax, (off[i + 1] - off[i] + kSsBlock - 1) / kSsBlock);
+    if (nbmax) {
+      SsBufs B;
+      if (int rc = ss_bufs(ctx, nbmax, B)) return rc;
+      if (hipMemsetAsync(todo, 0xff, (uint64_t)n * 4, s) != hipSuccess) return CPK_EDEVICE;
+      for (uint32_t i = 0; i < n; ++i) {
+        if (!takes(i)) continue;
+        const uint64_t len = off[i + 1] - off[i], nb = (len + kSsBlock - 1) / kSsBlock;
+        if (int rc = ss_map_launch(ctx, pk + off[i], len, nullptr, 0, nb, B, s)) return rc;
+        hipLaunchKernelGGL(us_end_kernel, dim3(1), dim3(64), 0, s, pk + off[i], nb, B, words + i, d_status + i,
+                           todo + i);
+      }
+      mapped = true;
+    }
+  }
+  if (dec_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
+  // persistent: workgroups of 4 independent waves, kUsWpe per CU
+  const unsigned want = (n + 3) / 4, full = (unsigned)(kUsWpe * ctx->cus);
+  hipLaunchKernelGGL(us_wave_kernel, dim3(want < full ? want : full), dim3(kUsThreads), kUsLds, s, pk, d_in_off, n,
+                     words, d_status, ctx->tickets + kTkDec, mapped ? (const uint32_t *)todo : (const uint32_t *)nullptr);
+  scan_launch(words, n, bsum, d_swo, s);
+  return hip_ok(hipGetLastError());
+}
+
+int cpk_unpacked_size_batch(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off, uint32_t n,
+                            uint64_t *d_seg_word_off, int32_t *d_status, void *stream) {
+  // (a batch of <= 32 pieces may read its extent back, as cpk_decode_batch
+  // does; not while the stream is being captured)
+  bool probe = n <= 32 && n > 0;
+  if (probe && ctx) {
+    DeviceGuard g(ctx->device);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+      probe = false;
+  }
+  return unpacked_size_impl(ctx, d_packed, d_in_off, n, d_seg_word_off, d_status, stream, probe, nullptr);
 }
 
 // A whole stream of unpacked messages packed (encode_ms.hip): the frame

@@ -832,6 +832,64 @@ int cpk_packed_size_messages_host(cpk_ctx ctx, const void *h_in, const uint64_t 
       });
 }
 
+// The unpacked-size query from host memory (cpk_unpacked_size_batch): chunks
+// of whole pieces of about CPK_HOST_CHUNK_MB packed bytes go up (a piece
+// larger than that is a chunk of its own, at the front of its slot: the
+// block map takes it), only the chunk's word offsets and statuses come back;
+// the offsets land at the running total of words.  The host knows every
+// chunk's offsets, so the device call reads nothing back.
+int cpk_unpacked_size_host(cpk_ctx ctx, const void *h_packed, const uint64_t *h_in_off, uint32_t n,
+                           uint64_t *h_seg_word_off, int32_t *h_status) {
+  if (!ctx || !h_seg_word_off || (n && (!h_in_off || !h_status))) return CPK_EINVAL;
+  h_seg_word_off[0] = 0;
+  if (n == 0) return CPK_OK;
+  for (uint32_t i = 0; i < n; ++i)
+    if (h_in_off[i + 1] < h_in_off[i]) return CPK_EINVAL;
+  if (!h_packed && h_in_off[n] > h_in_off[0]) return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  const uint8_t *src = (const uint8_t *)h_packed;
+  const uint64_t target = host_chunk_bytes();
+  std::vector<HostChunk> cs;
+  for (uint32_t i = 0; i < n;) {
+    HostChunk c{i, i, 0, 0, h_in_off[i], 0, 0, 0};
+    while (c.i1 < n && (c.i1 == c.i0 || h_in_off[c.i1 + 1] - c.in0 <= target)) ++c.i1;
+    c.in_len = h_in_off[c.i1] - c.in0;
+    cs.push_back(c);
+    i = c.i1;
+  }
+  uint64_t base = 0;
+  // meta: in_off [nk + 1] | seg_word_off [nk + 1] | status (int32, nk / 2 + 1 entries)
+  const int rc = run_chunks(
+      ctx, cs,
+      ChunkForm{false, false, 32, src,  // (the windows are loaded by whole 16-byte lines)
+                [](const HostChunk &c) -> uint64_t { return 2 * (c.i1 - c.i0 + 1ull) + (c.i1 - c.i0) / 2 + 1; }},
+      [&](uint8_t *pin, const HostChunk &c) { par_copy(pin, src + c.in0, c.in_len); },
+      [&](HostSlot &s, const HostChunk &c) {
+        const uint32_t nk = c.i1 - c.i0;
+        for (uint32_t j = 0; j <= nk; ++j) s.pin_meta[j] = h_in_off[c.i0 + j] - c.in0;
+        return nk + 1ull;
+      },
+      [&](HostSlot &s, const HostChunk &c, hipStream_t sk) {
+        const uint32_t nk = c.i1 - c.i0;
+        uint64_t *dswo = s.d_meta + nk + 1;
+        int32_t *st = (int32_t *)(s.d_meta + 2 * (nk + 1ull));
+        if (int r = unpacked_size_impl(ctx, s.d_in, s.d_meta, nk, dswo, st, sk, false, s.pin_meta)) return r;
+        return hip_ok(hipMemcpyAsync(s.pin_meta + nk + 1, dswo, (nk + 1) * 8ull + nk * 4ull, hipMemcpyDeviceToHost, sk));
+      },
+      [&](HostSlot &s, const HostChunk &c) {
+        const uint32_t nk = c.i1 - c.i0;
+        const uint64_t *coff = s.pin_meta + nk + 1;
+        for (uint32_t j = 0; j <= nk; ++j) h_seg_word_off[c.i0 + j] = base + coff[j];
+        base += coff[nk];
+        memcpy(h_status + c.i0, s.pin_meta + 2 * (nk + 1ull), nk * 4ull);
+        return ChunkOut{CPK_OK, (uint8_t *)s.pin_out, 0};
+      });
+  if (rc) return rc;
+  for (uint32_t i = 0; i < n; ++i)
+    if (h_status[i] != CPK_OK) return h_status[i];
+  return CPK_OK;
+}
+
 // Decode: chunks of whole messages by packed bytes.  A chunk's table pass
 // gives its words and segments; the chunk is then decoded straight into the
 // caller's arrays at the running totals.  When the caller's capacities are

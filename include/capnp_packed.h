@@ -233,6 +233,56 @@ int cpk_decode_batch(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off
                      const uint64_t *d_seg_word_off, uint32_t n, void *d_out,
                      int32_t *d_status, void *stream);
 
+/* Unpacked sizes without decoding: how many words each piece's packed bytes
+ * unpack to -- the d_seg_word_off every decode entry point must be given --
+ * for a caller that knows byte ranges and nothing else (length-prefixed packed
+ * blobs, pieces of cpk_encode_batch kept with d_out_off alone, packed bytes
+ * taken from outside, to be sized before anything is allocated for them: one
+ * 00 ff pair expands 2 bytes to 2 KiB).  The mirror image of
+ * cpk_packed_size_batch; upstream Cap'n Proto's C++ library has it as
+ * computeUnpackedSizeInWords.  Device traffic is the packed bytes, read once,
+ * plus 12 bytes per piece.
+ *   Piece i is the packed bytes [d_in_off[i], d_in_off[i+1]), parsed from
+ *     fresh state as PackedInputStream.java:82-134 reads records.
+ *   d_packed        : 16-byte aligned, readable up to round_up(d_in_off[n], 16)
+ *                     as for cpk_decode_batch.  It is only read.
+ *   d_in_off        : uint64[n+1], device.
+ *   d_seg_word_off  : uint64[n+1], device, written: [0] = 0, [i+1] - [i] =
+ *                     piece i's words, [n] = the total.  It can be handed to
+ *                     cpk_decode_batch as it stands.
+ *   d_status        : int32[n], device, written: CPK_OK when the range ends
+ *                     exactly at a record's end (an empty range is CPK_OK with
+ *                     0 words); CPK_ETRUNC when it ends inside a record: a tag
+ *                     without all its bytes, 00 without its count, ff without
+ *                     its word and count, a literal run cut short.  No other
+ *                     status can occur: CPK_EOVERRUN and CPK_ETRAILING need a
+ *                     word count to be measured against.
+ * A piece that is not CPK_OK sizes to 0 words: cpk_decode_batch given these
+ * offsets then reports CPK_ETRAILING for that piece and writes nothing for it
+ * (its behaviour for 0 words and a nonempty range), and the good pieces
+ * decode.  For a CPK_OK piece the size is the one and only word count for
+ * which cpk_decode_batch returns CPK_OK on that range.
+ * The device form is asynchronous on `stream` and returns CPK_OK once
+ * launched; CPK_EINVAL for missing or misaligned pointers.  n == 0 is valid:
+ * [0] = 0.  cpk_ctx_take_error is not involved.  As cpk_decode_batch does, a
+ * batch of at most 32 pieces reads its extent back (one sync of `stream`; not
+ * while the stream is being captured): a piece of n * 64 KiB or more is then
+ * sized by the 256-byte block map over its own bytes (a piece that starts off
+ * a 16-byte line, or whose map is irregular, by one wave like the others).
+ * A piece of more than 2^32-1 packed bytes is handled as cpk_decode_batch
+ * handles it: the wave-per-piece form, like the batch decoders, takes the
+ * range's length modulo 2^32 (the result is then that of the shorter range,
+ * not an error), and only the block-map path of a batch of at most 32 pieces
+ * measures in 64 bits, as that call's stream path does.
+ * The host form is synchronous: the packed bytes go up through the context's
+ * pinned chunk pipeline in chunks of whole pieces (CPK_HOST_CHUNK_MB), only
+ * the offsets and statuses come back.  It returns CPK_OK iff every piece is
+ * CPK_OK, otherwise the first failed piece's status, as cpk_decode_host. */
+int cpk_unpacked_size_batch(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off,
+                            uint32_t n, uint64_t *d_seg_word_off, int32_t *d_status, void *stream);
+int cpk_unpacked_size_host(cpk_ctx ctx, const void *h_packed, const uint64_t *h_in_off,
+                           uint32_t n, uint64_t *h_seg_word_off, int32_t *h_status);
+
 /* Stream decode (Serialize.read over PackedInputStream, Serialize.java:
  * 165-175): pieces 0..n-1 are decoded back to back from one packed stream of
  * `avail` bytes; each piece's read() stops when the piece is full and leaves
