@@ -43,6 +43,7 @@ EXPORTS = [
     "cpk_packed_size_batch", "cpk_packed_size_messages", "cpk_packed_size_host",
     "cpk_packed_size_messages_host",
     "cpk_unpacked_size_batch", "cpk_unpacked_size_host",
+    "cpk_encode_batch_at",
 ]
 MSG_HEAD_WORDS, MSG_INFO_WORDS = 257, 517  # CPK_MSG_HEAD_WORDS, CPK_MSG_INFO_WORDS
 MS_INFO_WORDS = 5  # CPK_MS_INFO_WORDS
@@ -124,6 +125,7 @@ def load(path: Path | None = None, strict: bool = True) -> ctypes.CDLL:
         "cpk_packed_size_messages_host": ([vp, vp, vp, u32, vp, u32, vp], i32),
         "cpk_unpacked_size_batch": ([vp, vp, vp, u32, vp, vp, vp], i32),
         "cpk_unpacked_size_host": ([vp, vp, vp, u32, vp, vp], i32),
+        "cpk_encode_batch_at": ([vp, vp, vp, u32, u64, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         if not strict and not hasattr(L, name):
@@ -702,6 +704,28 @@ def _unpacked_size_host(self, packed: np.ndarray, in_off: np.ndarray):
     return swo, st[:n]
 
 
+def _encode_batch_at(self, d_in, d_seg_word_off, max_seg_words: int, d_grp_piece_off, d_out, out_cap: int,
+                     d_dst_off, d_dst_cap, d_piece_off, d_grp_len, d_status, stream=None, ng=None):
+    """cpk_encode_batch_at: the pieces packed to where the caller says.  Group
+    g (pieces d_grp_piece_off[g] .. [g+1]; None: every piece its own group)
+    goes to d_out + d_dst_off[g], into a slot of d_dst_cap[g] bytes (None: to
+    out_cap -- d_dst_off may then be packed_size_batch's output as it stands).
+    Written: d_piece_off[n], d_grp_len[ng], d_status[ng] (OK, ENOMEM for a slot
+    too small or past out_cap, EINVAL for a piece over max_seg_words); no byte
+    of d_out outside the groups' packed bytes is touched.  ng: the group count
+    when it is not d_grp_piece_off's (or, without groups, the piece count)."""
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    n = d_seg_word_off.numel() - 1
+    if ng is None:
+        ng = d_grp_piece_off.numel() - 1 if d_grp_piece_off is not None else n
+    rc = self._lib.cpk_encode_batch_at(self.handle, ptr(d_in), d_seg_word_off.data_ptr(), n, int(max_seg_words),
+                                       ptr(d_grp_piece_off), int(ng), ptr(d_out), int(out_cap), ptr(d_dst_off),
+                                       ptr(d_dst_cap), ptr(d_piece_off), ptr(d_grp_len), ptr(d_status),
+                                       self._stream(stream))
+    _check(rc, "cpk_encode_batch_at")
+
+
+Context.encode_batch_at = _encode_batch_at
 Context.packed_size_batch = _packed_size_batch
 Context.unpacked_size_batch = _unpacked_size_batch
 Context.unpacked_size_host = _unpacked_size_host

@@ -42,6 +42,8 @@ struct cpk_ctx_s {
                           // 2 the emit pass only, 0 neither (CPK_E4_ORDER)
   int size_form;          // cpk_packed_size_batch: 0 by piece size, 1 chunk parallel, 2 wave per piece (CPK_SIZE_FORM)
   int usize_form;         // cpk_unpacked_size_batch: 0 by piece size, 1 block map, 2 wave per piece (CPK_USIZE_FORM)
+  int at_form;            // cpk_encode_batch_at: 0 by density, 1 dense, 2 sparse (CPK_AT_FORM)
+  DevBuf at_buf;          // cpk_encode_batch_at with groups: the groups' first units [ng + 1] | the pieces' groups [n]
   // CPK_HOST_TRACE=1 (read at creation): host wall time of the one-message
   // host paths (cpk_encode_host[_gather], cpk_read_message_host) by phase,
   // summed per context and printed to stderr by cpk_ctx_destroy
@@ -304,6 +306,9 @@ int cpk_ctx_create(int device, cpk_ctx *out) {
     // map for every piece it can take, a wave per piece (A/B of its threshold)
     const char *u = getenv("CPK_USIZE_FORM");
     c->usize_form = (u && u[0] == '1') ? 1 : (u && u[0] == '2') ? 2 : 0;
+    // CPK_AT_FORM=dense / sparse forces the placed encoder's form (A/B of its gate)
+    const char *a = getenv("CPK_AT_FORM");
+    c->at_form = (a && a[0] == 'd') ? 1 : (a && a[0] == 's') ? 2 : 0;
   }
   if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
     c->cus = 256;
@@ -330,6 +335,7 @@ int cpk_ctx_create(int device, cpk_ctx *out) {
              {(const void *)cpk::decode_kernel<true, true>, cpk::kDecLds},
              {(const void *)cpk::sp_encode_kernel<true>, cpk::SpLay<cpk::SpDense>::kLds},
              {(const void *)cpk::sp_encode_kernel<false>, cpk::SpLay<cpk::SpDense>::kLds},
+             {(const void *)cpk::sp_place_kernel<cpk::SpDense>, cpk::SpLay<cpk::SpDense>::kLds},
              {(const void *)cpk::sp_small_kernel, cpk::kSpSmallLds},
              {(const void *)cpk::rm_mw_kernel, cpk::kMwLds},
              {(const void *)cpk::stream_mw_kernel, cpk::kMwLds},
@@ -357,7 +363,7 @@ void cpk_ctx_destroy(cpk_ctx ctx) {
   }
   // (every DevBuf member: a new one is added here)
   for (DevBuf *b : {&ctx->status, &ctx->sp_status, &ctx->sp_desc, &ctx->sp_units, &ctx->e4_bv, &ctx->ss_buf,
-                    &ctx->ms_buf, &ctx->ems_buf, &ctx->rm_buf, &ctx->fl_buf, &ctx->rm_copy})
+                    &ctx->ms_buf, &ctx->ems_buf, &ctx->rm_buf, &ctx->fl_buf, &ctx->rm_copy, &ctx->at_buf})
     if (b->p) hipFree(b->p);
   if (ctx->tickets) hipFree(ctx->tickets);
   if (ctx->probe_pin) hipHostFree(ctx->probe_pin);
@@ -780,6 +786,75 @@ int cpk_packed_size_messages(cpk_ctx ctx, const void *d_in, const uint64_t *d_sw
   if (np > 0xffffffffull) return CPK_EINVAL;
   MsgPass M;
   if (int rc = msg_front(ctx, d_in, d_swo, nseg, d_msg_seg_off, nm, max_seg_words, d_out_off, s, false, M)) return rc;
+  return hip_ok(hipGetLastError());
+}
+
+// ---- encode to caller-given offsets (encode_at.hip) -------------------------
+// The single pass's plan (sp_plan: units, status words, epoch), the piece ->
+// group map (at_prep_kernel) and both forms of sp_place_kernel, enqueued for
+// the device to choose (at_gate_kernel over e4_minmax_kernel's sample).
+int cpk_encode_batch_at(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, uint64_t max_seg_words,
+                        const uint64_t *d_grp_piece_off, uint32_t ng, void *d_out, uint64_t out_cap,
+                        const uint64_t *d_dst_off, const uint64_t *d_dst_cap, uint64_t *d_piece_off,
+                        uint64_t *d_grp_len, int32_t *d_status, void *stream) {
+  if (!ctx || (!d_swo && n) || (!d_piece_off && n)) return CPK_EINVAL;
+  if (ng && (!d_dst_off || !d_grp_len || !d_status || !d_out)) return CPK_EINVAL;
+  if (d_grp_piece_off ? (ng == 0 && n != 0) : ng != n) return CPK_EINVAL;
+  if (((uintptr_t)d_out & 15) || ((uintptr_t)d_in & 7) || ((uintptr_t)d_status & 3)) return CPK_EINVAL;
+  for (const void *q : {(const void *)d_swo, (const void *)d_grp_piece_off, (const void *)d_dst_off,
+                        (const void *)d_dst_cap, (const void *)d_piece_off, (const void *)d_grp_len})
+    if ((uintptr_t)q & 7) return CPK_EINVAL;
+  if (ng == 0) return CPK_OK;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  // (no offset or length of a real buffer is near 2^64: the kernels' byte
+  // addresses then never wrap)
+  if (out_cap > (1ull << 62)) out_cap = 1ull << 62;
+  cpk::AtArgs A = {(const uint64_t *)d_in, d_swo,      n,           ng,        (uint8_t *)d_out, out_cap, d_dst_off,
+                   d_dst_cap,              nullptr,    nullptr,     d_piece_off, d_grp_len,      d_status};
+  const unsigned tb = 256, gg = (ng + tb - 1) / tb;
+  if (n == 0) {
+    // (groups without pieces: their statuses and lengths)
+    hipLaunchKernelGGL(cpk::at_prep_kernel, dim3(gg), dim3(tb), 0, s, A, d_grp_piece_off,
+                       (const uint64_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr);
+    return hip_ok(hipGetLastError());
+  }
+  // a bound on the batch's 8192-word units (0: every piece is one): from the
+  // hint; with no hint, or one so loose that the unit table it bounds would
+  // pass 2^25 entries, from the batch's word count read back (synchronising
+  // the stream, as cpk_encode_batch without a hint)
+  uint64_t ub = max_seg_words ? sp_unit_bound(n, max_seg_words) : 0;
+  if (!max_seg_words || ub > (1ull << 25))
+    if (int rc = sp_batch_unit_bound(ctx, d_swo, n, 0, s, ub)) return rc;
+  if (ub > 0xffffffffull) return CPK_EUNSUPPORTED;
+  uint32_t samples;
+  if (int rc = gate_arm(ctx, d_swo, n, true, d_in, s, samples)) return rc;
+  hipLaunchKernelGGL(cpk::at_gate_kernel, dim3(1), dim3(64), 0, s, ctx->tickets, samples, (uint32_t)ctx->at_form);
+  SpPlan P;
+  if (int rc = sp_plan(ctx, d_swo, nullptr, n, max_seg_words, ub, s, P)) return rc;
+  // (the pieces' first units: the scan the unit table was filled from)
+  const uint64_t *ustart = P.nunits ? P.nunits - n : nullptr;
+  uint64_t *gfirst = nullptr;
+  uint32_t *pgrp = nullptr;
+  if (d_grp_piece_off) {
+    if (int rc = carve_reserve(ctx->at_buf, 1024, [&](Carve &c) {
+          gfirst = c.take((uint64_t)ng + 1);
+          pgrp = c.take32(n);
+        }))
+      return rc;
+    if (hipMemsetAsync(pgrp, 0xff, (uint64_t)n * 4, s) != hipSuccess) return CPK_EDEVICE;
+  }
+  hipLaunchKernelGGL(cpk::at_prep_kernel, dim3(gg), dim3(tb), 0, s, A, d_grp_piece_off, ustart, pgrp, gfirst);
+  A.pgrp = pgrp;
+  A.gfirst = d_grp_piece_off ? gfirst : ustart;  // (a piece its own group: its first unit)
+  const uint32_t *pick = ctx->tickets + cpk::kTkGate + cpk::kGateSparse;
+  auto launch = [&](auto kernel, int wpe, uint32_t lds, uint32_t form) {
+    hipLaunchKernelGGL(kernel, dim3(sp_grid(ctx, wpe, P)), dim3(cpk::kSpThreads), lds, s, A, P.status, P.epoch,
+                       ctx->tickets + cpk::kTkPlan, P.utab, P.nunits, P.ustate, max_seg_words,
+                       ctx->tickets + cpk::kTkErr, pick, form);
+  };
+  launch(cpk::sp_place_kernel<cpk::SpDense>, cpk::SpDense::kWpe, cpk::SpLay<cpk::SpDense>::kLds, 0u);
+  launch(cpk::sp_place_kernel<cpk::SpSparse>, cpk::SpSparse::kWpe, cpk::SpLay<cpk::SpSparse>::kLds, 1u);
   return hip_ok(hipGetLastError());
 }
 

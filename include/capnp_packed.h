@@ -217,6 +217,62 @@ int cpk_packed_size_messages_host(cpk_ctx ctx, const void *h_in, const uint64_t 
                                   uint32_t nseg, const uint64_t *h_msg_seg_off, uint32_t nm,
                                   uint64_t *h_out_off);
 
+/* Encode to caller-given offsets: the pieces of cpk_encode_batch, packed to
+ * where the caller says -- into an allocation of exactly the size
+ * cpk_packed_size_batch reported, behind a length prefix or record header the
+ * caller writes itself, or each message into a slot of its own (a ring-buffer
+ * entry, a send buffer per peer) in any order.  A slot that is too small is
+ * refused as the reference's sink refuses a write that does not fit
+ * (ArrayOutputStream.write, ArrayOutputStream.java:36-44).
+ *   Pieces: d_in, d_seg_word_off[n+1], max_seg_words as for cpk_encode_batch
+ *     (0 = unknown: d_seg_word_off[0], [n] are read back, synchronising
+ *     `stream`; so is a bound so loose that n pieces of it would make more than
+ *     2^25 chunks of 8192 words).
+ *   Groups: group g is the pieces [d_grp_piece_off[g], d_grp_piece_off[g+1]),
+ *     uint64[ng+1], device, [0] = 0 and [ng] = n.  The pieces of a group are
+ *     packed back to back, each from fresh run state (bit-exact with the
+ *     reference's write() per piece), as cpk_encode_batch packs a whole batch.
+ *     d_grp_piece_off == NULL: ng must equal n, every piece is its own group.
+ *     A message is a group whose first piece is its table words; this call
+ *     builds no tables.
+ *   Placement: group g's first byte is d_out + d_dst_off[g] (uint64[ng], any
+ *     byte alignment, slots in any order) and its slot is d_dst_cap[g] bytes
+ *     (uint64[ng]).  d_dst_cap == NULL: every slot runs to out_cap -- d_dst_off
+ *     may then be the first n entries of what cpk_packed_size_batch wrote, as
+ *     they stand.  d_out is 16-byte aligned, out_cap its bytes.  Slots of
+ *     different groups must not overlap (overlapping slots leave their bytes
+ *     undefined; nothing outside [0, out_cap) is stored even then).
+ *   Written: d_piece_off[n], the absolute byte offset in d_out of every
+ *     piece's first packed byte; d_grp_len[ng], the group's exact packed bytes,
+ *     also when it did not fit; d_status[ng], int32, every entry:
+ *       CPK_OK;
+ *       CPK_ENOMEM when d_grp_len[g] > d_dst_cap[g] or the slot passes out_cap
+ *         (no byte outside the group's own slot is stored, the bytes inside it
+ *         are undefined);
+ *       CPK_EINVAL when a piece of the group is larger than a nonzero
+ *         max_seg_words (or 2^31 words and more): it is sized 0, the group's
+ *         bytes and length are undefined.
+ *   Bytes of d_out that belong to no group's packed bytes are never written:
+ *     not the gaps between slots, not the unused tail of a slot, not the bytes
+ *     that share a 16-byte line with the start or end of a group.
+ * Asynchronous on `stream`, no host synchronisation when max_seg_words != 0;
+ * cpk_ctx_take_error is not involved.  n == 0 or ng == 0 is valid.  Missing or
+ * misaligned pointers, or d_grp_piece_off == NULL with ng != n: CPK_EINVAL.
+ * The kernel is the single pass (a workgroup per 8192-word chunk) with each
+ * group's base given: a group of one piece of at most one chunk waits for no
+ * other; the chunks of a larger group look back over that group only.  Its
+ * dense or sparse form is chosen on the device from a sample of the words
+ * (CPK_AT_FORM=dense|sparse, read at context creation, forces one).  There is
+ * no host form: the host encoders' packed bytes already pass through pinned
+ * staging, from where the caller's own memcpy places them. */
+int cpk_encode_batch_at(cpk_ctx ctx, const void *d_in, const uint64_t *d_seg_word_off, uint32_t n,
+                        uint64_t max_seg_words,
+                        const uint64_t *d_grp_piece_off, uint32_t ng,
+                        void *d_out, uint64_t out_cap,
+                        const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
+                        uint64_t *d_piece_off, uint64_t *d_grp_len, int32_t *d_status,
+                        void *stream);
+
 /* Batch decode of n pieces, device-resident (replaces n calls of
  * PackedInputStream.read, PackedInputStream.java:35-140).
  *   d_packed        : packed bytes, readable up to round_up(d_in_off[n], 16).
