@@ -282,9 +282,21 @@ int cpk_encode_batch_at(cpk_ctx ctx, const void *d_in, const uint64_t *d_seg_wor
  *   d_status        : int32[n], device, written per piece (CPK_* codes).
  * Returns CPK_OK if launched; per-piece results are in d_status.  A batch of
  * at most 32 pieces reads its extent back (one sync of `stream`): with
- * >= 8 Mi words per piece on average it is decoded as one stream, 256-byte
- * blocks in parallel, the batch decoders running after it only when some
- * piece did not end exactly at its packed range's end. */
+ * >= 8 MiB of words (1 Mi words) per piece on average it is decoded as one
+ * stream, 256-byte blocks in parallel, the batch decoders running after it
+ * only when some piece did not end exactly at its packed range's end.
+ * Confinement (the packed bytes may come from outside): whatever a piece's
+ * status, no word outside [d_seg_word_off[0], d_seg_word_off[n]) is written
+ * and no entry outside d_status[0..n); d_packed, d_in_off and d_seg_word_off
+ * are only read.  A piece whose packed range is empty and whose word count is
+ * not 0 is CPK_ETRUNC and no word is written for it.  The words of any other
+ * piece that is not CPK_OK are undefined; the words of a CPK_OK piece are the
+ * reference's, whatever its neighbours' statuses.  One exception: a batch
+ * that takes the one-stream path above (at most 32 pieces, 1 Mi words each on
+ * average) reads on across piece boundaries before the batch decoders set
+ * the statuses, so there words may be written for a failed piece with an
+ * empty range too (the bounds of the first sentence are cpk_decode_stream's
+ * there, which are the same). */
 int cpk_decode_batch(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off,
                      const uint64_t *d_seg_word_off, uint32_t n, void *d_out,
                      int32_t *d_status, void *stream);
@@ -345,7 +357,13 @@ int cpk_unpacked_size_host(cpk_ctx ctx, const void *h_packed, const uint64_t *h_
  * the rest to the next (PackedInputStream.java:35-140), so no packed offsets
  * are needed.  d_in_off[n+1] is written with the piece boundaries found
  * (d_in_off[n] = bytes consumed).  A failed piece stops the stream: it and
- * every later piece get its status.  Asynchronous on `stream`. */
+ * every later piece get its status.  Asynchronous on `stream`.
+ * Confinement, as for cpk_decode_batch: whatever the statuses, no word outside
+ * [d_seg_word_off[0], d_seg_word_off[n]) is written and no entry outside
+ * d_status[0..n) and d_in_off[0..n]; d_packed and d_seg_word_off are only
+ * read.  The words of the pieces before the first failed one are the
+ * reference's and their boundaries exact; the words and boundaries of the
+ * failed piece and of every later one are undefined. */
 int cpk_decode_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
                       const uint64_t *d_seg_word_off, uint32_t n, void *d_out,
                       uint64_t *d_in_off, int32_t *d_status, void *stream);

@@ -1,6 +1,8 @@
 """Packed pieces built from records, for the decoder seam tests (no GPU, no
 pytest; tests/test_packed_records.py pins this file against the oracle,
-tests/test_gpu_decoder_seams.py feeds the corpora to every decoder form).
+tests/test_gpu_decoder_seams.py feeds the corpora to every decoder form,
+tests/test_gpu_decoder_confinement.py checks that nothing is written outside
+the pieces).
 
 A piece is a list of records, so the builder knows every record's packed byte
 position and first output word (PackedInputStream.java:82-134 reads exactly
@@ -359,11 +361,14 @@ class Case:
     """(name, packed bytes, word count) and what the builder knows of it:
     words (None for a malformed case), canonical, expect (the status name the
     builder predicts; the oracle's answer is the authority), tag (the probe's
-    byte position), style."""
-    __slots__ = ("name", "packed", "nwords", "words", "canonical", "expect", "tag", "kind", "style")
+    byte position), style; where the builder placed a probe with a tail behind
+    it, word (the probe's first output word) and tail (the bytes behind it)."""
+    __slots__ = ("name", "packed", "nwords", "words", "canonical", "expect", "tag", "kind", "style", "word", "tail")
 
-    def __init__(self, name, b: Built, style, tag=None, kind=None, packed=None, nwords=None, expect="OK"):
+    def __init__(self, name, b: Built, style, tag=None, kind=None, packed=None, nwords=None, expect="OK",
+                 word=None, tail=None):
         self.name, self.style, self.tag, self.kind, self.expect = name, style, tag, kind, expect
+        self.word, self.tail = word, tail
         self.packed = b.packed if packed is None else packed
         self.nwords = b.nwords if nwords is None else nwords
         valid = expect == "OK"
@@ -387,7 +392,8 @@ def first_window_seams(style: str):
                 tail = TAILS[n % 4]
                 n += 1
                 b = filled(p, style) + probe(kind) + filled(tail, style, 1)
-                cases.append(Case(f"win{S}/{kind}/tag@{p - S:+d}/{style}/tail{tail}", b, style, tag=p, kind=kind))
+                cases.append(Case(f"win{S}/{kind}/tag@{p - S:+d}/{style}/tail{tail}", b, style, tag=p, kind=kind,
+                                  word=filled(p, style).nwords, tail=tail))
     return cases
 
 
@@ -401,8 +407,9 @@ def _place_at_window_edge(style, w, off, kind, win, tail_bytes):
     keep = [r for r, (p, _, _) in zip(base, idx) if p + len(r.packed) <= target - 150]
     head = built(keep)
     gap = target - len(head.packed)
-    b = head + filled(gap, style, 2) + probe(kind) + filled(tail_bytes, style, 3)
-    return b, target
+    head = head + filled(gap, style, 2)
+    b = head + probe(kind) + filled(tail_bytes, style, 3)
+    return b, target, head.nwords
 
 
 def later_window_seams():
@@ -413,8 +420,10 @@ def later_window_seams():
     for w in (1, 2):
         for kind in PROBES:
             for off in range(-2, 3):
-                b, tag = _place_at_window_edge("dense", w, off, kind, kWin, 2 * kWin + 300)
-                cases.append(Case(f"winedge{w}|{w + 1}/{kind}/tag@{off:+d}/dense", b, "dense", tag=tag, kind=kind))
+                tail = 2 * kWin + 300
+                b, tag, word = _place_at_window_edge("dense", w, off, kind, kWin, tail)
+                cases.append(Case(f"winedge{w}|{w + 1}/{kind}/tag@{off:+d}/dense", b, "dense", tag=tag, kind=kind,
+                                  word=word, tail=tail))
     return cases
 
 
@@ -426,8 +435,9 @@ def wave_wrap_seams():
         for kind in PROBES:
             for off in range(-2, 3):
                 tail = (kMwWaves + 1 - w) * kWin + 300
-                b, tag = _place_at_window_edge("dense", w, off, kind, kWin, tail)
-                cases.append(Case(f"wrap{w}|{w + 1}/{kind}/tag@{off:+d}/dense", b, "dense", tag=tag, kind=kind))
+                b, tag, word = _place_at_window_edge("dense", w, off, kind, kWin, tail)
+                cases.append(Case(f"wrap{w}|{w + 1}/{kind}/tag@{off:+d}/dense", b, "dense", tag=tag, kind=kind,
+                                  word=word, tail=tail))
     return cases
 
 
@@ -446,7 +456,8 @@ def output_word_seams(style: str):
                 head = built(fill_words(R - d, style))
                 assert len(head.packed) < 2100 and head.nrec < kD2NI - 8 and head.nwords == R - d
                 b = head + probe(kind) + filled(40, style, 1)
-                cases.append(Case(f"round{R}/{kind}/word@{-d:+d}/{style}", b, style, tag=len(head.packed), kind=kind))
+                cases.append(Case(f"round{R}/{kind}/word@{-d:+d}/{style}", b, style, tag=len(head.packed), kind=kind,
+                                  word=R - d, tail=40))
     return cases
 
 
@@ -564,9 +575,7 @@ def first_window_cuts(cases):
     the tag, before the count byte, in the middle of the literals and one
     byte before its end (the word count stays the whole piece's)."""
     out = []
-    for c in cases:
-        if not c.name.startswith(f"win{kWin}/") or not -2 <= c.tag - kWin <= 2:
-            continue
+    for c in first_window_edge_cases(cases):
         k = int(c.kind[1:])
         cuts = {"tag": c.tag + 1, "end-1": len(c.packed) - 1}
         if c.kind[0] == "F":
@@ -578,6 +587,97 @@ def first_window_cuts(cases):
             out.append(Case(f"{c.name}/cut@{what}", Built(c.packed, c.words), c.style, c.tag, c.kind,
                             packed=c.packed[:at], expect="ETRUNC"))
     return out
+
+
+FULL_VARIANTS = ("full@probe", "full+1", "full@end-1", "full@end")
+
+
+def full_variants(c: Case):
+    """The word counts at which the piece of valid case c is full at or
+    inside its probe (first word o, nw words, t bytes behind it), while its
+    packed bytes go on: [(variant, nwords, expect)].
+
+      full@probe  o           the record before the probe fills the piece
+      full+1      o + 1       the probe's run overruns after its first word
+      full@end-1  o + nw - 1  ... one word before its end
+      full@end    o + nw      the probe fills the piece, the tail is left
+    """
+    o, nw, t = c.word, probe(c.kind).nwords, c.tail
+    out = []
+    if o > 0:
+        out.append(("full@probe", o, "ETRAILING"))
+    if nw > 1:
+        out.append(("full+1", o + 1, "EOVERRUN"))
+    if nw > 2:
+        out.append(("full@end-1", o + nw - 1, "EOVERRUN"))
+    if t > 0:
+        out.append(("full@end", o + nw, "ETRAILING"))
+    return out
+
+
+def full_before_the_end(cases):
+    """Every variant of full_variants for each valid case: the case's bytes,
+    only the word count changed, so the piece is full with its tail (and, but
+    for full@end, the rest of the probe) unread.  With a tail of two bytes or
+    more also as /tailcut: the last packed byte dropped, so the bytes end
+    inside a record windows behind the full point.  The reference stops at
+    the full point: the status stays what it was."""
+    out = []
+    for c in cases:
+        assert c.expect == "OK" and c.word is not None and c.tail is not None and c.kind in PROBES + WORD_PROBES
+        b = Built(c.packed, c.words)
+        for v, nwords, expect in full_variants(c):
+            assert 0 < nwords < c.nwords
+            out.append(Case(f"{c.name}/{v}", b, c.style, c.tag, c.kind, nwords=nwords, expect=expect,
+                            word=c.word, tail=c.tail))
+            if c.tail >= 2:
+                out.append(Case(f"{c.name}/{v}/tailcut", b, c.style, c.tag, c.kind, packed=c.packed[:-1],
+                                nwords=nwords, expect=expect, word=c.word, tail=c.tail - 1))
+    return out
+
+
+FULL_LONG_TAIL = 2 * kWin
+FULL_LONG_KINDS = ("Z255", "F255")
+
+
+def output_word_seams_long_tail(style: str):
+    """output_word_seams' pieces for the probe at word R exactly, with two
+    windows of bytes behind the probe instead of 40 bytes (valid cases, used
+    only as sources of full_before_the_end: a full point on a round edge
+    whose tail ends windows later)."""
+    cases = []
+    for R in WORD_SEAMS:
+        for kind in FULL_LONG_KINDS:
+            head = built(fill_words(R, style))
+            b = head + probe(kind) + filled(FULL_LONG_TAIL, style, 1)
+            cases.append(Case(f"round{R}/{kind}/word@+0/{style}/tail{FULL_LONG_TAIL}", b, style,
+                              tag=len(head.packed), kind=kind, word=R, tail=FULL_LONG_TAIL))
+    return cases
+
+
+def first_window_edge_cases(cases):
+    """The first-window S = kWin cases with tag offset -2..+2 (what
+    first_window_cuts cuts)."""
+    return [c for c in cases if c.name.startswith(f"win{kWin}/") and -2 <= c.tag - kWin <= 2]
+
+
+FULL_WRAP_KINDS = ("Z255", "F255", "F1", "T1")
+# source corpora of each full/* corpus (full_sources picks from them)
+FULL_SOURCES = {"full/words-sparse": ("words/sparse",), "full/words-mid": ("words/mid",),
+                "full/first": tuple(f"first/{s}" for s in STYLES), "full/later": ("later/dense",),
+                "full/wrap": ("wrap/dense",)}
+
+
+def full_sources(c: dict, name: str):
+    """The valid cases a full/* corpus is derived from."""
+    src = [x for s in FULL_SOURCES[name] for x in c[s]]
+    if name.startswith("full/words-"):
+        return src + output_word_seams_long_tail(name.split("-")[1])
+    if name == "full/first":
+        return first_window_edge_cases(src)
+    if name == "full/wrap":
+        return [x for x in src if "/tag@+0/" in x.name and x.kind in FULL_WRAP_KINDS]
+    return src
 
 
 # ---- batches and streams -----------------------------------------------------
@@ -668,6 +768,8 @@ def corpora() -> dict:
     for style in ("dense", "mid"):
         c[f"end/{style}"], c[f"endbad/{style}"] = end_of_piece_edges(style)
     c["cuts"] = first_window_cuts([x for s in STYLES for x in c[f"first/{s}"]])
+    for name in FULL_SOURCES:
+        c[name] = full_before_the_end(full_sources(c, name))
     return c
 
 
@@ -680,7 +782,7 @@ def release():
 
 VALID = ("first/sparse", "first/mid", "first/dense", "first/z0pair", "later/dense", "wrap/dense", "words/sparse",
          "words/mid", "rounds/sparse", "count/mid", "count/dense", "noncanon", "end/dense", "end/mid")
-MALFORMED = ("endbad/dense", "endbad/mid", "cuts")
+MALFORMED = ("endbad/dense", "endbad/mid", "cuts") + tuple(FULL_SOURCES)
 # what dec_gate_kernel does with each batch when the decoder is not forced
 GATE = {"first/sparse": "index", "words/sparse": "index", "rounds/sparse": "index",
         "first/mid": "map", "first/z0pair": "map", "count/mid": "map", "end/mid": "map",

@@ -9,9 +9,10 @@ import _packed_records as R
 
 # Bytes one GPU call may move: the limit holds for every corpus and for the
 # concatenated stream, each of which is what one GPU test sends, not for
-# their sum.  The sweeps as specified come to about 91 MiB packed and 322 MiB
+# their sum.  The sweeps as specified come to about 120 MiB packed and 450 MiB
 # unpacked together (the first-window corpora alone to 49 MiB packed, the
-# malformed end-of-piece variants to 19 MiB), so a limit on the sum could
+# malformed end-of-piece variants to 19 MiB, the full-before-the-end variants
+# to 29 MiB), so a limit on the sum could
 # only be met by thinning them; test_corpus_totals prints the sum.
 LIMIT_PACKED, LIMIT_WORDS = 64 << 20, 256 << 20
 
@@ -104,6 +105,82 @@ def test_malformed_cases_fail_as_predicted(oracle, corpora, malformed_status, na
     assert {"ETRUNC"} <= set(malformed_status.values())
     if name.startswith("endbad"):
         assert {c.expect for c in cases} == {"ETRUNC", "EOVERRUN", "ETRAILING"}
+    if name.startswith("full/"):
+        # full before the bytes end: the reference stops at the full point, so
+        # never ETRUNC, whatever the tail ends in
+        assert {c.expect for c in cases} == {"EOVERRUN", "ETRAILING"}
+
+
+FULL_SEAMS = {
+    "full/words-sparse": ({f"round{Rd}" for Rd in R.WORD_SEAMS}, R.WORD_PROBES),
+    "full/words-mid": ({f"round{Rd}" for Rd in R.WORD_SEAMS}, R.WORD_PROBES),
+    "full/first": ({f"win{R.kWin}"}, R.PROBES),
+    "full/later": ({"winedge1|2", "winedge2|3"}, R.PROBES),
+    "full/wrap": ({f"wrap{R.kMwWaves - 1}|{R.kMwWaves}", f"wrap{R.kMwWaves}|{R.kMwWaves + 1}"}, R.FULL_WRAP_KINDS),
+}
+
+
+def _window_of(starts, pos):
+    return sum(s <= pos for s in starts) - 1
+
+
+@pytest.mark.parametrize("name", list(R.FULL_SOURCES))
+def test_full_point_variants_cover_their_sources(corpora, name):
+    """Every full/* corpus against the bytes of its valid sources, read back
+    with parse_records: each (seam, probe kind) of the source selection is
+    there; the probe is a record of its kind at word o with t bytes behind
+    it; every variant whose condition holds (full@probe: o > 0, full+1:
+    nw > 1, full@end-1: nw > 2, full@end: t > 0) is present with the source's
+    bytes and its word count, and cut by one byte when t >= 2; nothing else
+    is.  Some /tailcut case loses its byte in a later window than the one it
+    is full in, by the block map's windows and by the record index's."""
+    src = R.full_sources(corpora, name)
+    got = {c.name: c for c in corpora[name]}
+    assert len(got) == len(corpora[name])
+    seams, kinds = FULL_SEAMS[name]
+    assert {(c.name.split("/")[0], c.kind) for c in src} == {(s, k) for s in seams for k in kinds}
+    if name == "full/first":
+        assert {c.name.split("/")[3] for c in src} == set(R.STYLES)
+        assert {c.tag - R.kWin for c in src} == {-2, -1, 0, 1, 2} and {c.tail for c in src} == set(R.TAILS)
+    if name == "full/wrap":
+        assert all("/tag@+0/" in c.name for c in src)
+    if name.startswith("full/words-"):
+        # the full point R - d (+ 0, 1, nw - 1, nw) takes every phase of the kBlk-word block at every round edge
+        for Rd in R.WORD_SEAMS:
+            full = {c.nwords - Rd for c in corpora[name] if c.name.startswith(f"round{Rd}/")}
+            assert set(range(-8, 2)) <= full, Rd
+    want, later = set(), {R.kWin: 0, R.kD2Win: 0}
+    for c in src:
+        idx = R.parse_records(c.packed)
+        i = next(i for i, (p, _, _) in enumerate(idx) if p == c.tag)
+        o, kind = idx[i][1], idx[i][2]
+        nw = (idx[i + 1][1] if i + 1 < len(idx) else c.nwords) - o
+        t = len(c.packed) - (idx[i + 1][0] if i + 1 < len(idx) else len(c.packed))
+        assert (kind, o, t) == (c.kind, c.word, c.tail), c.name
+        variants = {"full@probe": (o, o > 0), "full+1": (o + 1, nw > 1), "full@end-1": (o + nw - 1, nw > 2),
+                    "full@end": (o + nw, t > 0)}
+        assert set(variants) == set(R.FULL_VARIANTS)
+        for v, (nwords, holds) in variants.items():
+            for cut in ("", "/tailcut"):
+                full = f"{c.name}/{v}{cut}"
+                if not (holds and (not cut or t >= 2)):
+                    assert full not in got, full
+                    continue
+                want.add(full)
+                x = got[full]
+                assert x.nwords == nwords and x.words is None and not x.canonical, full
+                assert x.packed == (c.packed[:-1] if cut else c.packed), full
+                if not cut:
+                    continue
+                # the record that fills (or overruns) the piece, and the record the cut lands in
+                j = max(k for k, (_, w, _) in enumerate(idx) if w <= nwords - 1)
+                for win, cap in ((R.kWin, None), (R.kD2Win, R.kD2NI)):
+                    starts = R.window_starts(idx, len(c.packed), win, cap)
+                    later[win] += _window_of(starts, idx[-1][0]) > _window_of(starts, idx[j][0])
+    assert want == set(got)
+    print(f"\n{name}: {len(src)} sources, {len(got)} cases; /tailcut cases cut in a later window than they are "
+          f"full in: {later[R.kWin]} (block map), {later[R.kD2Win]} (record index)")
+    assert later[R.kWin] > 0 and later[R.kD2Win] > 0
 
 
 def test_every_named_seam_is_present(corpora):
@@ -139,6 +216,18 @@ def test_every_named_seam_is_present(corpora):
             assert f"reccap{R.kD2NI}/{kind}/records{cnt}/mid" in names
     for cnt in (127, 128, 129):
         assert f"sermax{R.kDecSerMax}/F2/records{cnt}/dense/0" in names
+    # full before the bytes end (test_full_point_variants_cover_their_sources has the whole list)
+    for v in R.FULL_VARIANTS:
+        for cut in ("", "/tailcut"):
+            for Rd in (1280, 2560, 2048, 4096):
+                for style in ("sparse", "mid"):
+                    assert f"round{Rd}/Z255/word@-3/{style}/{v}{cut}" in names
+                    assert f"round{Rd}/F255/word@+0/{style}/tail{2 * R.kWin}/{v}{cut}" in names
+            for w in (1, 2):
+                assert f"winedge{w}|{w + 1}/F255/tag@-1/dense/{v}{cut}" in names
+                assert f"wrap{w + R.kMwWaves - 2}|{w + R.kMwWaves - 1}/Z255/tag@+0/dense/{v}{cut}" in names
+    for style in R.STYLES:
+        assert any(f"win{R.kWin}/F255/tag@+0/{style}/tail{t}/full+1" in names for t in R.TAILS)
     print(f"\n{n} first-window (seam, kind, offset, style) points; {len(names)} named cases")
 
 
