@@ -44,6 +44,7 @@ EXPORTS = [
     "cpk_packed_size_messages_host",
     "cpk_unpacked_size_batch", "cpk_unpacked_size_host",
     "cpk_encode_batch_at",
+    "cpk_decode_batch_at", "cpk_unpacked_size_batch_at",
 ]
 MSG_HEAD_WORDS, MSG_INFO_WORDS = 257, 517  # CPK_MSG_HEAD_WORDS, CPK_MSG_INFO_WORDS
 MS_INFO_WORDS = 5  # CPK_MS_INFO_WORDS
@@ -126,6 +127,8 @@ def load(path: Path | None = None, strict: bool = True) -> ctypes.CDLL:
         "cpk_unpacked_size_batch": ([vp, vp, vp, u32, vp, vp, vp], i32),
         "cpk_unpacked_size_host": ([vp, vp, vp, u32, vp, vp], i32),
         "cpk_encode_batch_at": ([vp, vp, vp, u32, u64, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp], i32),
+        "cpk_decode_batch_at": ([vp, vp, u64, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp], i32),
+        "cpk_unpacked_size_batch_at": ([vp, vp, u64, vp, vp, u32, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         if not strict and not hasattr(L, name):
@@ -725,7 +728,47 @@ def _encode_batch_at(self, d_in, d_seg_word_off, max_seg_words: int, d_grp_piece
     _check(rc, "cpk_encode_batch_at")
 
 
+def _decode_batch_at(self, d_packed, in_cap: int, d_src_off, d_src_len, d_grp_piece_off, d_seg_word_off, d_out,
+                     d_status, d_grp_status, d_grp_used, stream=None, ng=None):
+    """cpk_decode_batch_at: the pieces decoded from where the caller says.
+    Group g (pieces d_grp_piece_off[g] .. [g+1], read back to back; None: every
+    piece its own group) is the packed bytes d_packed[d_src_off[g] ..
+    d_src_off[g] + d_src_len[g]), any alignment, order and gaps, below in_cap.
+    Piece i goes to words d_seg_word_off[i] .. [i+1] of d_out.  Written:
+    d_status[n], d_grp_status[ng] (OK, the first failed piece's status,
+    ETRAILING, EINVAL for a range past in_cap, EUNSUPPORTED for one over 2^32-1
+    bytes), d_grp_used[ng].  The arrays of an encode_batch_at call decode what
+    it wrote: d_dst_off as d_src_off, d_grp_len as d_src_len.  ng: the group
+    count when it is not d_grp_piece_off's (or, without groups, the piece
+    count)."""
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    n = d_seg_word_off.numel() - 1 if d_seg_word_off is not None else 0
+    if ng is None:
+        ng = d_grp_piece_off.numel() - 1 if d_grp_piece_off is not None else n
+    rc = self._lib.cpk_decode_batch_at(self.handle, ptr(d_packed), int(in_cap), ptr(d_src_off), ptr(d_src_len),
+                                       ptr(d_grp_piece_off), int(ng), ptr(d_seg_word_off), n, ptr(d_out),
+                                       ptr(d_status), ptr(d_grp_status), ptr(d_grp_used), self._stream(stream))
+    _check(rc, "cpk_decode_batch_at")
+
+
+def _unpacked_size_batch_at(self, d_packed, in_cap: int, d_src_off, d_src_len, d_seg_word_off, d_status,
+                            stream=None):
+    """cpk_unpacked_size_batch_at: unpacked_size_batch over the ranges
+    d_packed[d_src_off[i] .. d_src_off[i] + d_src_len[i]): d_seg_word_off[n+1]
+    gets the word offsets decode_batch_at must be given, d_status[n] OK, ETRUNC,
+    or a refused range's EINVAL / EUNSUPPORTED (each sized 0).  Never
+    synchronises."""
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    n = d_seg_word_off.numel() - 1
+    rc = self._lib.cpk_unpacked_size_batch_at(self.handle, ptr(d_packed), int(in_cap), ptr(d_src_off),
+                                              ptr(d_src_len), n, d_seg_word_off.data_ptr(), ptr(d_status),
+                                              self._stream(stream))
+    _check(rc, "cpk_unpacked_size_batch_at")
+
+
 Context.encode_batch_at = _encode_batch_at
+Context.decode_batch_at = _decode_batch_at
+Context.unpacked_size_batch_at = _unpacked_size_batch_at
 Context.packed_size_batch = _packed_size_batch
 Context.unpacked_size_batch = _unpacked_size_batch
 Context.unpacked_size_host = _unpacked_size_host

@@ -378,7 +378,9 @@ __device__ __forceinline__ bool win_emit(const uint8_t *pkw, const uint64_t *lut
   return !failed;
 }
 
-template <bool kStream, bool kSerial = false>
+// (kAt: the batch form with a range per piece, in_off three words per piece
+// as DecPieces<false, true> takes them -- decode_at.hip)
+template <bool kStream, bool kSerial = false, bool kAt = false>
 __device__ __forceinline__ void decode_body(uint8_t *smem, const uint8_t *__restrict__ packed,
                                             uint64_t *__restrict__ in_off, const uint64_t *__restrict__ swo,
                                             uint32_t n, uint64_t *__restrict__ out, int32_t *__restrict__ status,
@@ -453,9 +455,9 @@ __device__ __forceinline__ void decode_body(uint8_t *smem, const uint8_t *__rest
     if (seg >= n) break;
     const uint64_t w0 = rfl64(swo[seg]);
     const int W = __builtin_amdgcn_readfirstlane((int)(swo[seg + 1] - w0));
-    const uint64_t a = rfl64(kStream ? scur : in_off[seg]);
+    const uint64_t a = rfl64(kStream ? scur : in_off[kAt ? 3 * (uint64_t)seg : seg]);
     const uint32_t P = kStream ? (uint32_t)min(slim - scur, (uint64_t)0xffffffffu)
-                               : (uint32_t)(in_off[seg + 1] - a);
+                               : (uint32_t)(in_off[kAt ? 3 * (uint64_t)seg + 1 : seg + 1] - a);
     if (kStream && sfail != CPK_OK) {
       status[seg] = sfail;
       if (seg + 1 == sende) sd.send_out[sj] = scur;
@@ -576,7 +578,14 @@ __device__ __forceinline__ void decode_body(uint8_t *smem, const uint8_t *__rest
       const bool failed = !win_emit<kStream, kDecLean>(pkw, lut, blk, lane, e, ow, W, P, T, wc.on, wc.entry, S,
                                                        wc.onmask, wc.o0, wc.myw, enext, lend, gp, glim, ph, dst, st,
                                                        fin, false DEC_PH_ARGS);
-      if (failed) break;
+      if (failed) {
+        // (kAt: a piece full before its range ends says where -- the lane that
+        // checked the filling record holds its end; written here, so nothing
+        // more is live across the window loop)
+        if constexpr (kAt && !kStream)
+          if (st == CPK_ETRAILING) in_off[3 * (uint64_t)seg + 2] = a + wave_max_u(fin);
+        break;
+      }
       if (ow + T >= W && fin) {  // the piece is full: next piece starts at fin
         ow = W;
         e = fin;

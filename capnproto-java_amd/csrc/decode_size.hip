@@ -65,6 +65,9 @@ struct UsPieces {
   }
 };
 
+// (us_wave_at_kernel, decode_at.hip, is this kernel's loop written out again
+// over a begin and an end array -- with the loop shared through an inlined
+// function this kernel's scalar registers moved: a change here goes there too)
 // words[i], status[i] of every piece i (todo: only of those with todo[i]
 // nonzero -- the pieces the block form left over)
 __global__ __launch_bounds__(kUsThreads, kUsWpe) void us_wave_kernel(const uint8_t *__restrict__ packed,

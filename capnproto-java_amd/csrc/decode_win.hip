@@ -104,7 +104,12 @@ struct DecStreams {
 // done() writes what it came to.  Batch pieces come from the per-XCD ticket
 // counters, a stream's pieces one after another from the stream a ticket
 // gave the wave.  Every value here is wave-uniform.
-template <bool kStream>
+// kAt (the batch form of cpk_decode_batch_at, decode_at.hip): in_off holds three
+//   words per piece -- its first packed byte, the end of its range (a range
+//   of its own), and, written by the decoder for a piece full before its
+//   range ends (CPK_ETRAILING), where the piece ended.  One array, so the
+//   form keeps no pointer the batch form does not.
+template <bool kStream, bool kAt = false>
 struct DecPieces {
   const uint64_t *swo;
   uint64_t *in_off;
@@ -176,8 +181,9 @@ struct DecPieces {
       if (seg >= n) return false;
       w0 = rfl64(swo[seg]);
       W = __builtin_amdgcn_readfirstlane((int)(swo[seg + 1] - w0));
-      a = rfl64(kStream ? scur : in_off[seg]);
-      P = kStream ? (uint32_t)min(slim - scur, (uint64_t)0xffffffffu) : (uint32_t)(in_off[seg + 1] - a);
+      a = rfl64(kStream ? scur : in_off[kAt ? 3 * (uint64_t)seg : seg]);
+      P = kStream ? (uint32_t)min(slim - scur, (uint64_t)0xffffffffu)
+                  : (uint32_t)(in_off[kAt ? 3 * (uint64_t)seg + 1 : seg + 1] - a);
       if (kStream && sfail != CPK_OK) {
         status[seg] = sfail;
         if (seg + 1 == sende) sd.send_out[sj] = scur;

@@ -1294,6 +1294,124 @@ int cpk_unpacked_size_batch(cpk_ctx ctx, const void *d_packed, const uint64_t *d
   return unpacked_size_impl(ctx, d_packed, d_in_off, n, d_seg_word_off, d_status, stream, probe, nullptr);
 }
 
+// ---- decode from caller-given ranges (decode_at.hip) -------------------------
+// The ranges checked and the batch's packed bytes summed (dat_prep_kernel), the
+// decoder chosen on the device from that sum (dat_gate_kernel; a forced
+// decoder alone), the groups' statuses and consumed bytes (dat_final_kernel).
+// No groups given: the batch forms on a range per piece; groups: the stream
+// forms, a wave per group, the groups with the most packed bytes first.
+int cpk_decode_batch_at(cpk_ctx ctx, const void *d_packed, uint64_t in_cap, const uint64_t *d_src_off,
+                        const uint64_t *d_src_len, const uint64_t *d_grp_piece_off, uint32_t ng,
+                        const uint64_t *d_seg_word_off, uint32_t n, void *d_out, int32_t *d_status,
+                        int32_t *d_grp_status, uint64_t *d_grp_used, void *stream) {
+  using namespace cpk;
+  if (!ctx || (n && (!d_seg_word_off || !d_status))) return CPK_EINVAL;
+  if (ng && (!d_src_off || !d_src_len || !d_grp_status || !d_grp_used)) return CPK_EINVAL;
+  if (d_grp_piece_off ? (ng == 0 && n != 0) : ng != n) return CPK_EINVAL;
+  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_status & 3) ||
+      ((uintptr_t)d_grp_status & 3))
+    return CPK_EINVAL;
+  for (const void *q : {(const void *)d_src_off, (const void *)d_src_len, (const void *)d_grp_piece_off,
+                        (const void *)d_seg_word_off, (const void *)d_grp_used})
+    if ((uintptr_t)q & 7) return CPK_EINVAL;
+  if (ng == 0) return CPK_OK;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  const bool grouped = d_grp_piece_off != nullptr;
+  // begin | end | pieces' end [ng]; the packed sum; with groups their lengths
+  // and order, and the pieces' starts the stream forms write
+  uint64_t *gbeg, *gend, *gout, *psum, *glen = nullptr, *pin = nullptr;
+  uint32_t *ord = nullptr, *ohist = nullptr;
+  if (int rc = carve_reserve(ctx->status, 1024, [&](Carve &c) {
+        gbeg = c.take(3ull * ng);  // (no groups: begin | end | out per piece, interleaved)
+        gend = gbeg ? gbeg + (grouped ? ng : 1) : nullptr;
+        gout = gbeg ? gbeg + (grouped ? 2ull * ng : 2) : nullptr;
+        psum = c.take(1);
+        if (grouped) {
+          glen = c.take(ng);
+          pin = c.take(n);
+          ord = c.take32(ng);
+          ohist = c.take32(kOrdClasses);
+        }
+      }))
+    return rc;
+  if (hipMemsetAsync(psum, 0, 8, s) != hipSuccess || dec_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
+  DatArgs A = {d_src_off, d_src_len, d_grp_piece_off, d_seg_word_off, n,          ng,
+               in_cap,    gbeg,      gend,            gout,           grouped ? 1u : 3u, d_grp_status};
+  const unsigned gg = (ng + kDatThreads - 1) / kDatThreads;
+  hipLaunchKernelGGL(dat_prep_kernel, dim3(gg), dim3(kDatThreads), 0, s, A, (unsigned long long *)psum, glen,
+                     (uint64_t *)nullptr, (uint32_t *)nullptr);
+  if (n) {
+    const uint8_t *pk = (const uint8_t *)d_packed;
+    uint32_t *skip = ctx->tickets + kTkGate + kGateDecSkip;  // [3]: kDecMap, kDecIndex, kDecDense
+    const bool gate = ctx->decoder == 3;
+    if (gate)
+      hipLaunchKernelGGL(dat_gate_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long *)psum, d_seg_word_off,
+                         n, skip);
+    if (grouped) ord_launch(glen, ng, ohist, ord, s);
+    // one form of the batch decoders on a range per piece
+    auto piece_launch = [&](DecKind k, const uint32_t *sk) {
+      const bool v2 = k == kDecIndex;
+      const uint32_t lds = v2 ? kD2Lds : kDecLds;
+      unsigned grid = (unsigned)min(8u, 160u * 1024u / lds) * (unsigned)ctx->cus;
+      if (grid > (n + 3) / 4) grid = (n + 3) / 4;
+      const auto kernel = v2 ? decode2_at_kernel : k == kDecDense ? decode_at_kernel<true> : decode_at_kernel<false>;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(v2 ? kD2Threads : kDecThreads), lds, s, pk, gbeg, d_seg_word_off, n,
+                         (uint64_t *)d_out, d_status, ctx->tickets + kTkDec, (uint64_t)0,
+                         DecStreams::batch(sk));
+    };
+    // (every form enqueued for the device to choose, the ones not picked
+    // return at once; a forced decoder alone, as decode_batch_impl)
+    for (int k = kDecMap; k <= kDecDense; ++k) {
+      if (!gate && k != (dec_v2(ctx) ? kDecIndex : kDecMap)) continue;
+      const uint32_t *sk = gate ? skip + (k - kDecMap) : nullptr;
+      if (grouped)
+        dec_launch(ctx, true, (ng + 3) / 4, pk, pin, d_seg_word_off, n, (uint64_t *)d_out, d_status, 0,
+                   DecStreams{gbeg, gend, d_grp_piece_off, ng, gout, sk, ord}, s, (DecKind)k);
+      else
+        piece_launch((DecKind)k, sk);
+    }
+  }
+  hipLaunchKernelGGL(dat_final_kernel, dim3(gg), dim3(kDatThreads), 0, s, A, d_status, d_grp_used);
+  return hip_ok(hipGetLastError());
+}
+
+// cpk_unpacked_size_batch over n ranges: the wave-per-piece form alone (no
+// read-back, no block map), refused ranges sized 0 by dat_prep_kernel.
+int cpk_unpacked_size_batch_at(cpk_ctx ctx, const void *d_packed, uint64_t in_cap, const uint64_t *d_src_off,
+                               const uint64_t *d_src_len, uint32_t n, uint64_t *d_seg_word_off, int32_t *d_status,
+                               void *stream) {
+  using namespace cpk;
+  if (!ctx || !d_seg_word_off || (n && (!d_src_off || !d_src_len || !d_status))) return CPK_EINVAL;
+  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_src_off & 7) || ((uintptr_t)d_src_len & 7) ||
+      ((uintptr_t)d_seg_word_off & 7) || ((uintptr_t)d_status & 3))
+    return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) return hip_ok(hipMemsetAsync(d_seg_word_off, 0, 8, s));
+  // words [n] | the scan's block sums | begin | end [n] | todo [n] (u32)
+  uint64_t *words, *bsum, *gbeg, *gend;
+  uint32_t *todo;
+  if (int rc = carve_reserve(ctx->status, 1024, [&](Carve &c) {
+        words = c.take(n);
+        bsum = c.take(scan_blocks(n) + 1);
+        gbeg = c.take(n);
+        gend = c.take(n);
+        todo = c.take32(n);
+      }))
+    return rc;
+  if (dec_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
+  DatArgs A = {d_src_off, d_src_len, nullptr, nullptr, n, n, in_cap, gbeg, gend, nullptr, 1u, d_status};
+  hipLaunchKernelGGL(dat_prep_kernel, dim3((n + kDatThreads - 1) / kDatThreads), dim3(kDatThreads), 0, s, A,
+                     (unsigned long long *)nullptr, (uint64_t *)nullptr, words, todo);
+  const unsigned want = (n + 3) / 4, full = (unsigned)(kUsWpe * ctx->cus);
+  hipLaunchKernelGGL(us_wave_at_kernel, dim3(want < full ? want : full), dim3(kUsThreads), kUsLds, s,
+                     (const uint8_t *)d_packed, (const uint64_t *)gbeg, (const uint64_t *)gend, n, words, d_status,
+                     ctx->tickets + kTkDec, (const uint32_t *)todo);
+  scan_launch(words, n, bsum, d_seg_word_off, s);
+  return hip_ok(hipGetLastError());
+}
+
 // A whole stream of unpacked messages packed (encode_ms.hip): the frame
 // chain over the words, its result row read back (the piece count sizes the
 // encoders' launches), the pieces through cpk_encode_batch_cap, then the

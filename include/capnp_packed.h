@@ -351,6 +351,95 @@ int cpk_unpacked_size_batch(cpk_ctx ctx, const void *d_packed, const uint64_t *d
 int cpk_unpacked_size_host(cpk_ctx ctx, const void *h_packed, const uint64_t *h_in_off,
                            uint32_t n, uint64_t *h_seg_word_off, int32_t *h_status);
 
+/* Decode from caller-given ranges: the pieces of cpk_decode_batch, each group
+ * of them read from the byte range the caller names -- the receiver's side of
+ * cpk_encode_batch_at: length-prefixed blobs, ring-buffer entries, a send
+ * buffer per peer, slots in any order, decoded where they lie with no
+ * compaction first.
+ *   Ranges: group g's packed bytes are d_packed + [d_src_off[g], d_src_off[g] +
+ *     d_src_len[g]), uint64[ng] each, device.  Any byte alignment, any order,
+ *     gaps between them; ranges may overlap or coincide: the input is only
+ *     read.  d_packed is 16-byte aligned and readable up to
+ *     round_up(in_cap, 16); no byte at or past that is read, and d_packed is
+ *     never written.
+ *   Groups: group g is the pieces [d_grp_piece_off[g], d_grp_piece_off[g+1]),
+ *     uint64[ng+1], device, [0] = 0 and [ng] = n.  The pieces of a group are
+ *     decoded back to back from the group's range, each read() from fresh
+ *     state; a piece that fills leaves the rest of the range to the next (the
+ *     stream rule of cpk_decode_stream, per group).  d_grp_piece_off == NULL:
+ *     ng must equal n, every piece is its own group.  No segment table is read
+ *     here: the caller gives every piece's word count.
+ *   Output: piece i goes to words [d_seg_word_off[i], d_seg_word_off[i+1]) of
+ *     d_out (8-byte aligned), tiled as in cpk_decode_batch -- so the offsets
+ *     cpk_unpacked_size_batch_at writes can be handed over as they stand.
+ *     There is no output scatter per piece.
+ *   Written: d_status[n], int32, one entry per piece; d_grp_status[ng], int32;
+ *     d_grp_used[ng], uint64: the bytes the group's pieces consumed.  The
+ *     group's status is
+ *       CPK_OK;
+ *       the first failed piece's status (CPK_ETRUNC, CPK_EOVERRUN): that piece
+ *         and every later piece of the group carry it, d_grp_used[g] is 0;
+ *       CPK_ETRAILING when all pieces filled before the range ended:
+ *         d_grp_used[g] < d_src_len[g] says by how much.  For a group of one
+ *         piece this is the batch form's CPK_ETRAILING, also in d_status;
+ *       CPK_EUNSUPPORTED when d_src_len[g] > 2^32-1: reported, not taken
+ *         modulo 2^32 as the batch form takes it (checked first: such a range
+ *         need not lie below in_cap to be told so);
+ *       CPK_EINVAL when the range passes in_cap (the sum computed
+ *         saturating), or for a piece of 2^31 words or more.
+ *     A group refused with the last two has nothing of its range read and
+ *     none of its words written; all its pieces carry its status and
+ *     d_grp_used[g] is 0.
+ *   Confinement, as for cpk_decode_batch: no word outside [d_seg_word_off[0],
+ *     d_seg_word_off[n]) is written.  A CPK_OK piece's words are the
+ *     reference's, whatever the other groups' statuses; a group's failure
+ *     touches no other group.  A piece with words and an empty range is
+ *     CPK_ETRUNC and no word is written for it.
+ * Round trip: the arrays of a cpk_encode_batch_at call decode what that call
+ * wrote -- d_dst_off as d_src_off, d_grp_len as d_src_len, the same
+ * d_grp_piece_off and d_seg_word_off.
+ * Asynchronous on `stream`, no host synchronisation at any n;
+ * cpk_ctx_take_error is not involved.  n == 0 or ng == 0 is valid.  Missing or
+ * misaligned pointers, or d_grp_piece_off == NULL with ng != n: CPK_EINVAL; a
+ * call that returns anything but CPK_OK writes nothing.  The decoder is chosen
+ * on the device as for cpk_decode_batch, from the ranges' summed bytes
+ * (CPK_DECODER forces one).
+ * Limit: a piece is decoded by one wave, whatever its size.  The "few large
+ * pieces as one stream" path of cpk_decode_batch needs a read-back and is not
+ * taken here: for one large range use cpk_decode_stream on it.  There is no
+ * host form. */
+int cpk_decode_batch_at(cpk_ctx ctx,
+                        const void *d_packed, uint64_t in_cap,
+                        const uint64_t *d_src_off, const uint64_t *d_src_len,
+                        const uint64_t *d_grp_piece_off, uint32_t ng,
+                        const uint64_t *d_seg_word_off, uint32_t n,
+                        void *d_out,
+                        int32_t *d_status, int32_t *d_grp_status, uint64_t *d_grp_used,
+                        void *stream);
+
+/* cpk_unpacked_size_batch over n ranges: piece i is the packed bytes d_packed +
+ * [d_src_off[i], d_src_off[i] + d_src_len[i]), placed as for
+ * cpk_decode_batch_at (any alignment and order, gaps, overlaps; d_packed
+ * 16-byte aligned, readable up to round_up(in_cap, 16), only read).
+ *   d_seg_word_off  : uint64[n+1], device, written: [0] = 0, [i+1] - [i] =
+ *                     piece i's words, [n] = the total; it can be handed to
+ *                     cpk_decode_batch_at as it stands.
+ *   d_status        : int32[n], device, written: CPK_OK, or CPK_ETRUNC with
+ *                     the piece sized 0, as cpk_unpacked_size_batch; and the
+ *                     two range statuses of cpk_decode_batch_at, the piece
+ *                     sized 0 and nothing of it read: CPK_EUNSUPPORTED for
+ *                     d_src_len[i] > 2^32-1, CPK_EINVAL for a range that
+ *                     passes in_cap.
+ * A piece sized 0 for a nonempty range is CPK_ETRAILING to cpk_decode_batch_at
+ * with nothing written, and the good pieces decode (a refused range stays
+ * refused there).  Asynchronous on `stream` with no host synchronisation: the
+ * wave-per-piece form only, no read-back and no block-map path.  n == 0 is
+ * valid: [0] = 0.  CPK_EINVAL for missing or misaligned pointers. */
+int cpk_unpacked_size_batch_at(cpk_ctx ctx,
+                               const void *d_packed, uint64_t in_cap,
+                               const uint64_t *d_src_off, const uint64_t *d_src_len, uint32_t n,
+                               uint64_t *d_seg_word_off, int32_t *d_status, void *stream);
+
 /* Stream decode (Serialize.read over PackedInputStream, Serialize.java:
  * 165-175): pieces 0..n-1 are decoded back to back from one packed stream of
  * `avail` bytes; each piece's read() stops when the piece is full and leaves
