@@ -45,7 +45,9 @@ EXPORTS = [
     "cpk_unpacked_size_batch", "cpk_unpacked_size_host",
     "cpk_encode_batch_at",
     "cpk_decode_batch_at", "cpk_unpacked_size_batch_at",
+    "cpk_decode_messages_at",
 ]
+MAT_TOTALS = 3  # CPK_MAT_TOTALS
 MSG_HEAD_WORDS, MSG_INFO_WORDS = 257, 517  # CPK_MSG_HEAD_WORDS, CPK_MSG_INFO_WORDS
 MS_INFO_WORDS = 5  # CPK_MS_INFO_WORDS
 EMS_INFO_WORDS = 6  # CPK_EMS_INFO_WORDS
@@ -129,6 +131,7 @@ def load(path: Path | None = None, strict: bool = True) -> ctypes.CDLL:
         "cpk_encode_batch_at": ([vp, vp, vp, u32, u64, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp], i32),
         "cpk_decode_batch_at": ([vp, vp, u64, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp], i32),
         "cpk_unpacked_size_batch_at": ([vp, vp, u64, vp, vp, u32, vp, vp, vp], i32),
+        "cpk_decode_messages_at": ([vp, vp, u64, vp, vp, u32, u64, vp, u64, vp, vp, vp, u32, vp, vp, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         if not strict and not hasattr(L, name):
@@ -766,8 +769,40 @@ def _unpacked_size_batch_at(self, d_packed, in_cap: int, d_src_off, d_src_len, d
     _check(rc, "cpk_unpacked_size_batch_at")
 
 
+def _decode_messages_at(self, d_packed, in_cap: int, d_src_off, d_src_len, d_out, d_seg_word_off, d_seg_in_off,
+                        d_seg_status, d_msg_seg_off, d_msg_status, d_msg_used, d_totals,
+                        traversal_limit_words: int = 8 * 1024 * 1024, stream=None, nm=None, out_cap_words=None,
+                        seg_cap=None):
+    """cpk_decode_messages_at: Serialize.read per message over the packed bytes
+    d_packed[d_src_off[m] .. d_src_off[m] + d_src_len[m]), any alignment, order
+    and gaps, below in_cap; the tables are read on the device and nothing comes
+    back to the host.  Capacities come from the tensors' sizes unless given;
+    d_out and the three segment arrays may be None (a sizing call).  Written:
+    d_msg_seg_off[nm+1], d_msg_status[nm] (OK, ETRAILING, a range's EINVAL /
+    EUNSUPPORTED, the table's or a segment's error, ENOMEM for an accepted
+    message past the capacities), d_msg_used[nm], d_totals[3] (the accepted
+    messages' words and segments, the messages that fit) and, for the fitting
+    messages, the words and the segment arrays as decode_messages tiles them.
+    Never synchronises."""
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    if nm is None:
+        nm = d_msg_seg_off.numel() - 1
+    if out_cap_words is None:
+        out_cap_words = d_out.numel() * d_out.element_size() // 8 if d_out is not None else 0
+    if seg_cap is None:
+        seg_cap = 0 if d_seg_word_off is None or d_seg_in_off is None or d_seg_status is None else \
+            min(d_seg_word_off.numel() - 1, d_seg_in_off.numel(), d_seg_status.numel())
+    rc = self._lib.cpk_decode_messages_at(self.handle, ptr(d_packed), int(in_cap), ptr(d_src_off), ptr(d_src_len),
+                                          int(nm), int(traversal_limit_words), ptr(d_out), int(out_cap_words),
+                                          ptr(d_seg_word_off), ptr(d_seg_in_off), ptr(d_seg_status), int(seg_cap),
+                                          ptr(d_msg_seg_off), ptr(d_msg_status), ptr(d_msg_used), ptr(d_totals),
+                                          self._stream(stream))
+    _check(rc, "cpk_decode_messages_at")
+
+
 Context.encode_batch_at = _encode_batch_at
 Context.decode_batch_at = _decode_batch_at
+Context.decode_messages_at = _decode_messages_at
 Context.unpacked_size_batch_at = _unpacked_size_batch_at
 Context.packed_size_batch = _packed_size_batch
 Context.unpacked_size_batch = _unpacked_size_batch

@@ -1412,6 +1412,96 @@ int cpk_unpacked_size_batch_at(cpk_ctx ctx, const void *d_packed, uint64_t in_ca
   return hip_ok(hipGetLastError());
 }
 
+// ---- messages from caller-given ranges (decode_msg_at.hip) --------------------
+// The tables read from the ranges (mat_table_kernel), the accepted messages'
+// words and segment counts scanned, the capacity verdict and the decoders'
+// piece ranges made on the device (mat_fit_kernel, mat_place_kernel), the
+// decoder chosen there too (dat_gate_kernel over the fitting messages; a
+// forced decoder alone), the stream forms a wave per message, the statuses and
+// consumed bytes (mat_final_kernel).  Nothing is read back: the host decides
+// on its own arguments only.
+int cpk_decode_messages_at(cpk_ctx ctx, const void *d_packed, uint64_t in_cap, const uint64_t *d_src_off,
+                           const uint64_t *d_src_len, uint32_t nm, uint64_t traversal_limit_words, void *d_out,
+                           uint64_t out_cap_words, uint64_t *d_seg_word_off, uint64_t *d_seg_in_off,
+                           int32_t *d_seg_status, uint32_t seg_cap, uint64_t *d_msg_seg_off, int32_t *d_msg_status,
+                           uint64_t *d_msg_used, uint64_t *d_totals, void *stream) {
+  using namespace cpk;
+  if (!ctx || !d_msg_seg_off || !d_totals) return CPK_EINVAL;
+  if (nm && (!d_src_off || !d_src_len || !d_msg_status || !d_msg_used)) return CPK_EINVAL;
+  if ((seg_cap && (!d_seg_word_off || !d_seg_in_off || !d_seg_status)) || (out_cap_words && !d_out))
+    return CPK_EINVAL;
+  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_seg_status & 3) ||
+      ((uintptr_t)d_msg_status & 3))
+    return CPK_EINVAL;
+  for (const void *q : {(const void *)d_src_off, (const void *)d_src_len, (const void *)d_seg_word_off,
+                        (const void *)d_seg_in_off, (const void *)d_msg_seg_off, (const void *)d_msg_used,
+                        (const void *)d_totals})
+    if ((uintptr_t)q & 7) return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (nm == 0) {
+    if (hipMemsetAsync(d_msg_seg_off, 0, 8, s) != hipSuccess) return CPK_EDEVICE;
+    return hip_ok(hipMemsetAsync(d_totals, 0, 8 * CPK_MAT_TOTALS, s));
+  }
+  // the messages' words | first segment bytes | range ends | streams' ends [nm];
+  // the words' scan | the decoders' piece ranges [nm + 1]; the two scans' block
+  // sums; the fit pass's words; the streams largest first
+  uint64_t *mwords, *mbeg, *mend, *mout, *mwoff, *spc, *bs0, *bs1, *fit;
+  uint32_t *ord, *ohist;
+  if (int rc = carve_reserve(ctx->status, 1024, [&](Carve &c) {
+        mwords = c.take(nm);
+        mbeg = c.take(nm);
+        mend = c.take(nm);
+        mout = c.take(nm);
+        mwoff = c.take((uint64_t)nm + 1);
+        spc = c.take((uint64_t)nm + 1);
+        bs0 = c.take(scan_blocks(nm));
+        bs1 = c.take(scan_blocks(nm));
+        fit = c.take(kMatWords);
+        ord = c.take32(nm);
+        ohist = c.take32(kOrdClasses);
+      }))
+    return rc;
+  if (hipMemsetAsync(fit + kMatNoFit, 0xff, 8, s) != hipSuccess ||
+      hipMemsetAsync(fit + kMatCount, 0, 16, s) != hipSuccess)
+    return CPK_EDEVICE;
+  const uint8_t *pk = (const uint8_t *)d_packed;
+  const unsigned tg = (nm + kMatThreads - 1) / kMatThreads, tg1 = nm / kMatThreads + 1;
+  // the segment counts go to d_msg_seg_off[0..nm) and are scanned into it, as
+  // cpk_decode_messages scans them
+  hipLaunchKernelGGL(mat_table_kernel, dim3(tg), dim3(kMatThreads), 0, s, pk, d_src_off, d_src_len, nm, in_cap,
+                     traversal_limit_words, mwords, d_msg_seg_off, mbeg, mend, d_msg_status);
+  scan_launch(mwords, nm, bs0, mwoff, s);
+  scan_launch(d_msg_seg_off, nm, bs1, d_msg_seg_off, s);
+  hipLaunchKernelGGL(mat_fit_kernel, dim3(tg), dim3(kMatThreads), 0, s, nm, (const uint64_t *)mwoff,
+                     (const uint64_t *)d_msg_seg_off, d_src_len, (const int32_t *)d_msg_status, out_cap_words,
+                     (uint64_t)seg_cap, (unsigned long long *)fit);
+  hipLaunchKernelGGL(mat_place_kernel, dim3(tg1), dim3(kMatThreads), 0, s, pk, d_src_off, d_src_len, nm,
+                     traversal_limit_words, (const uint64_t *)mwoff, (const uint64_t *)d_msg_seg_off, fit, mbeg, mend,
+                     spc, d_msg_status, d_seg_word_off, d_seg_in_off, d_totals);
+  // (no room for a segment: no message fits, there is nothing to decode)
+  if (seg_cap) {
+    if (dec_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
+    uint32_t *skip = ctx->tickets + kTkGate + kGateDecSkip;  // [3]: kDecMap, kDecIndex, kDecDense
+    const bool gate = ctx->decoder == 3;
+    if (gate)
+      hipLaunchKernelGGL(dat_gate_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long *)(fit + kMatBytes),
+                         (const uint64_t *)(fit + kMatGate), 1u, skip);
+    ord_launch(mwords, nm, ohist, ord, s);
+    // (every form enqueued for the device to choose, a forced decoder alone, as
+    // cpk_decode_batch_at)
+    for (int k = kDecMap; k <= kDecDense; ++k) {
+      if (!gate && k != (dec_v2(ctx) ? kDecIndex : kDecMap)) continue;
+      dec_launch(ctx, true, (nm + 3) / 4, pk, d_seg_in_off, d_seg_word_off, seg_cap, (uint64_t *)d_out, d_seg_status, 0,
+                 DecStreams{mbeg, mend, spc, nm, mout, gate ? skip + (k - kDecMap) : nullptr, ord}, s, (DecKind)k);
+    }
+  }
+  hipLaunchKernelGGL(mat_final_kernel, dim3(tg), dim3(kMatThreads), 0, s, nm, d_src_off, d_src_len,
+                     (const uint64_t *)spc, (const uint64_t *)mout, (const int32_t *)d_seg_status, d_msg_status,
+                     d_msg_used);
+  return hip_ok(hipGetLastError());
+}
+
 // A whole stream of unpacked messages packed (encode_ms.hip): the frame
 // chain over the words, its result row read back (the piece count sizes the
 // encoders' launches), the pieces through cpk_encode_batch_cap, then the

@@ -892,6 +892,7 @@ __global__ void gather8_kernel(Gather8 g, uint32_t k, uint64_t *out) {
 #include "stream_split.hip"
 #include "decode_size.hip"
 #include "decode_at.hip"
+#include "decode_msg_at.hip"
 #include "encode_ms.hip"
 
 }  // namespace cpk

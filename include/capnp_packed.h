@@ -368,7 +368,8 @@ int cpk_unpacked_size_host(cpk_ctx ctx, const void *h_packed, const uint64_t *h_
  *     state; a piece that fills leaves the rest of the range to the next (the
  *     stream rule of cpk_decode_stream, per group).  d_grp_piece_off == NULL:
  *     ng must equal n, every piece is its own group.  No segment table is read
- *     here: the caller gives every piece's word count.
+ *     here: the caller gives every piece's word count
+ *     (cpk_decode_messages_at reads the tables from the slots).
  *   Output: piece i goes to words [d_seg_word_off[i], d_seg_word_off[i+1]) of
  *     d_out (8-byte aligned), tiled as in cpk_decode_batch -- so the offsets
  *     cpk_unpacked_size_batch_at writes can be handed over as they stand.
@@ -485,6 +486,85 @@ int cpk_decode_messages(cpk_ctx ctx, const void *d_packed, const uint64_t *d_msg
                         uint64_t *d_seg_word_off, uint64_t *d_seg_in_off, int32_t *d_seg_status,
                         uint32_t seg_cap, uint64_t *d_msg_seg_off, int32_t *d_msg_status,
                         uint64_t *h_totals, void *stream);
+
+/* Decode messages from caller-given ranges: cpk_decode_messages' framing on
+ * cpk_decode_batch_at's ranges -- what a receiver of packed messages holds:
+ * ring-buffer entries, length-prefixed records, a send buffer per peer.  The
+ * segment tables are read from the slots where they lie, so the caller gives
+ * byte ranges and no word counts, and the capacity verdict is made on the
+ * device: the call never returns to the host between the tables and the
+ * decode.  Semantics: SerializePacked.read on each range (Serialize.read over
+ * PackedInputStream, Serialize.java:119-178).
+ *   Ranges: message m is the packed bytes d_packed + [d_src_off[m],
+ *     d_src_off[m] + d_src_len[m]), uint64[nm] each, device.  Any byte
+ *     alignment, any order, gaps; ranges may overlap or coincide: the input is
+ *     only read.  d_packed is 16-byte aligned and readable up to
+ *     round_up(in_cap, 16); no byte at or past that is read.  A range is
+ *     refused before a byte of it is read, as cpk_decode_batch_at refuses it:
+ *     CPK_EUNSUPPORTED for d_src_len[m] > 2^32-1 (checked first), CPK_EINVAL
+ *     for a range that passes in_cap (the sum computed saturating).
+ *   Table: read from the front of the range as cpk_decode_messages reads it
+ *     (the first word, then 4 * (count & ~1) bytes) with the same checks in
+ *     the same order: count <= 512, sizes >= 0, total <=
+ *     traversal_limit_words, segments <= 2^28-1 words.  A failed table gives
+ *     the message its status (CPK_EFRAME, CPK_ETRUNC, CPK_EOVERRUN), no
+ *     segments and no words.
+ *   Capacity: a message whose range and table are good is accepted.
+ *     d_totals[CPK_MAT_TOTALS], uint64, device, written whatever the
+ *     capacities: [0] the words and [1] the segments of all accepted
+ *     messages, [2] the accepted messages that fit.  Message m fits iff, over
+ *     the accepted messages in index order, its words end at or below
+ *     out_cap_words and its segments at or below seg_cap: the fitting
+ *     messages are a prefix of the accepted ones.  An accepted message that
+ *     does not fit is CPK_ENOMEM: nothing past its table is read, and no
+ *     word, segment entry or segment status is written for it.  d_out and the
+ *     three segment arrays may be NULL with capacities 0: every accepted
+ *     message is then CPK_ENOMEM and d_totals says what to allocate -- one
+ *     preliminary call sizes everything.
+ *   d_msg_seg_off : uint64[nm+1], written in full: [0] = 0, [m+1] - [m] the
+ *     table's count for an accepted message, fitting or not, 0 otherwise;
+ *     [nm] = d_totals[1] (values may exceed seg_cap).
+ *   For the fitting messages the segments are tiled in message order in d_out
+ *     (8-byte aligned) as cpk_decode_messages tiles them: d_seg_word_off[j]
+ *     and [j+1] bound segment j's words, d_seg_in_off[j] is the absolute byte
+ *     offset in d_packed of its first packed byte, d_seg_status[j] its status
+ *     (a failed segment stops its message: the later segments of that message
+ *     carry its status, and their d_seg_in_off is 0).  With F the segments'
+ *     end of the last fitting message, d_seg_word_off is written for [0, F],
+ *     d_seg_in_off and d_seg_status for [0, F), nothing beyond.  There is no
+ *     output scatter per message.
+ *   d_msg_status  : int32[nm], written, in this precedence: the range's
+ *     status; the table's; CPK_ENOMEM; the first failed segment's;
+ *     CPK_ETRAILING when the segments end before the range does; CPK_OK.
+ *   d_msg_used    : uint64[nm], written: the bytes consumed, table plus
+ *     segments, when the status is CPK_OK or CPK_ETRAILING -- where a ring
+ *     reader finds the next record --, otherwise 0.
+ *   Confinement: no word outside [0, out_cap_words) of d_out is written, no
+ *     entry past seg_cap (seg_cap + 1 for d_seg_word_off) or nm (nm + 1 for
+ *     d_msg_seg_off).  A CPK_OK message's words are the reference's, whatever
+ *     its neighbours' statuses; a failed message touches no other message.
+ * Round trip: groups encoded by cpk_encode_batch_at whose first piece is the
+ * table's words are messages; d_dst_off and d_grp_len of that call serve as
+ * d_src_off and d_src_len.
+ * Asynchronous on `stream`, no host synchronisation and no read-back at any
+ * nm; cpk_ctx_take_error is not involved.  nm == 0 is valid:
+ * d_msg_seg_off[0] = 0, d_totals = {0, 0, 0}.  Missing or misaligned pointers
+ * (the checks of cpk_decode_batch_at; an array may be NULL only where its
+ * capacity or nm is 0): CPK_EINVAL, and nothing is written.  The decoder is
+ * chosen on the device from the fitting messages' bytes and words
+ * (CPK_DECODER forces one).
+ * Limits: a message is decoded by one wave, as in cpk_decode_messages.  There
+ * is no host form. */
+#define CPK_MAT_TOTALS 3
+int cpk_decode_messages_at(cpk_ctx ctx,
+                           const void *d_packed, uint64_t in_cap,
+                           const uint64_t *d_src_off, const uint64_t *d_src_len, uint32_t nm,
+                           uint64_t traversal_limit_words,
+                           void *d_out, uint64_t out_cap_words,
+                           uint64_t *d_seg_word_off, uint64_t *d_seg_in_off, int32_t *d_seg_status,
+                           uint32_t seg_cap,
+                           uint64_t *d_msg_seg_off, int32_t *d_msg_status, uint64_t *d_msg_used,
+                           uint64_t *d_totals, void *stream);
 
 /* One message from the front of a packed byte stream whose length is not
  * known in advance (SerializePacked.read / readFromUnbuffered: Serialize.read
