@@ -258,7 +258,7 @@ class Context:
         """Serialize.read-style decode of pieces back to back from one packed
         stream of `avail` bytes (cpk_decode_stream); d_in_off[n+1] gets the
         piece boundaries found.  Synchronises `stream` once for streams of
-        256 KiB and more (they are cut into blocks and decoded in parallel)."""
+        384 KiB and more (they are cut into blocks and decoded in parallel)."""
         n = d_seg_word_off.numel() - 1
         rc = self._lib.cpk_decode_stream(self.handle, d_packed.data_ptr(), int(avail),
                                          d_seg_word_off.data_ptr(), n, d_out.data_ptr(),

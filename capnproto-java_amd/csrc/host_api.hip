@@ -71,6 +71,31 @@ struct TrClock {
 namespace {
 int hip_ok(hipError_t e) { return e == hipSuccess ? CPK_OK : CPK_EDEVICE; }
 
+// hipMemsetAsync for the device entry points, safe under graph capture.  A
+// memset captured into a graph is a memset node, and the HIP runtime this was
+// found on leaves part of such a node's range unset from the second launch of
+// the graph on (2,176 bytes: the last 544 keep their old values; a plain HIP
+// program shows it, tests/test_gpu_graph_replay.py found it: ticket counters
+// and a counting sort's histogram not cleared, then stores out of bounds).
+// So while `s` is being captured the bytes are set by a kernel node instead;
+// an uncaptured call is the hipMemsetAsync it always was.  p: 4-byte aligned
+// in every use here (any other pointer takes hipMemsetAsync).
+__global__ void fill_kernel(uint8_t *p, uint32_t v4, uint64_t bytes) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t nw = bytes / 4;
+  for (uint64_t k = i; k < nw; k += step) reinterpret_cast<uint32_t *>(p)[k] = v4;
+  if (i < (bytes & 3)) p[4 * nw + i] = (uint8_t)v4;
+}
+hipError_t fill_async(void *p, int value, size_t bytes, hipStream_t s) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  const bool captured = hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+  if (!captured || ((uintptr_t)p & 3) || bytes == 0) return hipMemsetAsync(p, value, bytes, s);
+  const uint64_t blocks = (bytes / 4 + 255) / 256;
+  hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks > 1024 ? 1024 : blocks)), dim3(256), 0, s,
+                     (uint8_t *)p, 0x01010101u * (uint32_t)(value & 0xff), (uint64_t)bytes);
+  return hipGetLastError();
+}
+
 struct DeviceGuard {
   int prev;
   explicit DeviceGuard(int d) {
@@ -89,7 +114,7 @@ struct DeviceGuard {
 void ord_launch(const uint64_t *words, uint32_t n, uint32_t *hist, uint32_t *order, hipStream_t s,
                 const uint64_t *swo = nullptr) {
   const unsigned tb = 256, tg = (n + tb - 1) / tb;
-  (void)hipMemsetAsync(hist, 0, 4 * cpk::kOrdClasses, s);
+  (void)fill_async(hist, 0, 4 * cpk::kOrdClasses, s);
   hipLaunchKernelGGL(cpk::ord_hist_kernel, dim3(tg), dim3(tb), 0, s, words, n, hist, swo);
   hipLaunchKernelGGL(cpk::ord_scan_kernel, dim3(1), dim3(64), 0, s, hist);
   hipLaunchKernelGGL(cpk::ord_scatter_kernel, dim3(tg), dim3(tb), 0, s, words, n, hist, order, swo);
@@ -109,13 +134,13 @@ void scan_launch(const uint64_t *in, uint32_t n, uint64_t *bsum, uint64_t *out, 
 
 // the decoders' ticket counters (one per XCD) back to zero
 hipError_t dec_tickets_reset(cpk_ctx ctx, hipStream_t s) {
-  return hipMemsetAsync(ctx->tickets + cpk::kTkDec, 0, 8 * cpk::kTkStride * 4, s);
+  return fill_async(ctx->tickets + cpk::kTkDec, 0, 8 * cpk::kTkStride * 4, s);
 }
 
 // every ticket counter and the plan ticket (the words below the error word)
 // back to zero: before the two passes and the size calls
 hipError_t enc_tickets_reset(cpk_ctx ctx, hipStream_t s) {
-  return hipMemsetAsync(ctx->tickets, 0, cpk::kTkErr * 4, s);
+  return fill_async(ctx->tickets, 0, cpk::kTkErr * 4, s);
 }
 
 // the two passes' grid: persistent blocks of kE4Waves waves, a wave per piece
@@ -132,7 +157,7 @@ int ss_map_launch(cpk_ctx ctx, const uint8_t *pk, uint64_t reach, const uint64_t
                   const cpk::SsBufs &B, hipStream_t s) {
   using namespace cpk;
   const uint64_t ng = (nb + kSsGroup - 1) / kSsGroup;
-  if (hipMemsetAsync(B.N2, 0, 4 * nb, s) != hipSuccess || hipMemsetAsync(B.flag, 0, 8, s) != hipSuccess ||
+  if (fill_async(B.N2, 0, 4 * nb, s) != hipSuccess || fill_async(B.flag, 0, 8, s) != hipSuccess ||
       dec_tickets_reset(ctx, s) != hipSuccess)
     return CPK_EDEVICE;
   const unsigned tb = 256, gb = (unsigned)((nb + tb - 1) / tb);
@@ -404,7 +429,8 @@ static int read_words(cpk_ctx ctx, hipStream_t s, std::initializer_list<const ui
 }
 
 // Single-pass encoder (encode_sp.hip): one launch, the look-back words
-// epoch-tagged (cleared only when the epoch wraps or the array grows).  Work
+// epoch-tagged (cleared only when the epoch wraps or the array grows, and by
+// every launch captured into a graph, as a node of that graph: sp_plan).  Work
 // is ticketed per 8192-word chunk of a piece (a unit); a batch whose pieces
 // may be larger than one chunk (the hint) first gets its unit table (three
 // small kernels and the e4 scan, no host sync: the unit count stays on the
@@ -444,9 +470,12 @@ static bool sp_takes(cpk_ctx ctx, uint32_t n, uint64_t max_seg_words) {
 struct SpPlan {
   uint64_t ucap;                  // units at most
   uint64_t *status, *ustate;      // look-back words [ucap] | run-state words [ucap]
-  uint32_t epoch;                 // 1..65535
+  uint32_t epoch;                 // 1..65535; kSpEpochCaptured for a launch being captured into a graph
   const uint64_t *utab, *nunits;  // the unit table and its count on the device; null: every piece one unit
 };
+// the epoch of every captured launch: the tag of a cleared word, so only words
+// the launch's own graph wrote after its own clear can carry a flag under it
+constexpr uint32_t kSpEpochCaptured = 0;
 // `units`: a bound on the batch's units when its pieces may exceed one chunk
 // (0: every piece is one unit).  pdesc, hint: as the kernels take them.
 static int sp_plan(cpk_ctx ctx, const uint64_t *d_swo, const uint64_t *pdesc, uint32_t n, uint64_t hint,
@@ -456,14 +485,24 @@ static int sp_plan(cpk_ctx ctx, const uint64_t *d_swo, const uint64_t *pdesc, ui
   // cleared below, as when the epoch wraps)
   bool fresh = false;
   if (int rc = reserve(ctx->sp_status, 2 * P.ucap, 8192, nullptr, &fresh)) return rc;
-  if (++ctx->sp_epoch > 0xffffu) {
+  // A launch captured into a graph runs again at every replay with the
+  // arguments it was captured with, the epoch among them: the words the last
+  // replay left would be valid for the next.  So a captured launch takes no
+  // epoch from the counter: it is tagged kSpEpochCaptured, which no eager
+  // launch ever draws (the counter runs 1..65535), and the clear of the words
+  // it polls is enqueued ahead of it, a node of the graph.  (A status query
+  // that fails is taken for a capture: the clear is never wrong.)
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  const bool captured = hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+  if (!captured && ++ctx->sp_epoch > 0xffffu) {
     ctx->sp_epoch = 1;
     fresh = true;
   }
-  if (fresh && hipMemsetAsync(ctx->sp_status.p, 0, ctx->sp_status.cap * 8, s) != hipSuccess) return CPK_EDEVICE;
+  const uint64_t clear = fresh ? ctx->sp_status.cap : captured ? 2 * P.ucap : 0;
+  if (clear && fill_async(ctx->sp_status.p, 0, clear * 8, s) != hipSuccess) return CPK_EDEVICE;
   P.status = ctx->sp_status.p;
   P.ustate = P.status + P.ucap;
-  P.epoch = ctx->sp_epoch;
+  P.epoch = captured ? kSpEpochCaptured : ctx->sp_epoch;
   P.utab = P.nunits = nullptr;
   if (!units) return CPK_OK;
   // unit counts -> starts (e4 scan) -> unit table
@@ -496,7 +535,7 @@ int sp_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, const uint64
   if (int rc = sp_plan(ctx, d_swo, pdesc, n, hint, units, s, P)) return rc;
   // (gated: the ticket was set by e4_gate_kernel -- exhausted unless the
   // batch is the single pass's)
-  if (!gated && hipMemsetAsync(ctx->tickets + cpk::kTkPlan, 0, 4, s) != hipSuccess) return CPK_EDEVICE;
+  if (!gated && fill_async(ctx->tickets + cpk::kTkPlan, 0, 4, s) != hipSuccess) return CPK_EDEVICE;
   // (gated: both forms enqueued, the one the gate did not pick returns at once)
   const uint32_t *pick = gated ? ctx->tickets + cpk::kTkGate + cpk::kGateSparse : nullptr;
   // (tin: the tables' words of a message batch, the output bound before them)
@@ -567,11 +606,11 @@ static void e4_emit_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo,
 static int gate_arm(cpk_ctx ctx, const uint64_t *d_swo, uint32_t n, bool sampled, const void *d_in, hipStream_t s,
                     uint32_t &samples) {
   uint32_t *mm = ctx->tickets + cpk::kTkGate;
-  if (hipMemsetAsync(mm + cpk::kGateMin, 0xff, 4, s) != hipSuccess ||
-      hipMemsetAsync(mm + cpk::kGateMax, 0, 4, s) != hipSuccess)
+  if (fill_async(mm + cpk::kGateMin, 0xff, 4, s) != hipSuccess ||
+      fill_async(mm + cpk::kGateMax, 0, 4, s) != hipSuccess)
     return CPK_EDEVICE;
-  if (sampled && (hipMemsetAsync(mm + cpk::kGateZero, 0, 4, s) != hipSuccess ||
-                  hipMemsetAsync(mm + cpk::kGateBytes, 0, 4, s) != hipSuccess))
+  if (sampled && (fill_async(mm + cpk::kGateZero, 0, 4, s) != hipSuccess ||
+                  fill_async(mm + cpk::kGateBytes, 0, 4, s) != hipSuccess))
     return CPK_EDEVICE;
   const unsigned mg = n < 256u * 256u ? (unsigned)((n + 255) / 256) : 256u;
   hipLaunchKernelGGL(cpk::e4_minmax_kernel, dim3(mg), dim3(256), 0, s, d_swo, n, mm,
@@ -673,7 +712,7 @@ int cpk_encode_messages_cap(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo
   if (max_seg_words == 0) return CPK_EINVAL;  // (a bound is needed for the step rows)
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
-  if (nm == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
+  if (nm == 0) return hip_ok(fill_async(d_out_off, 0, 8, s));
   const uint64_t np = (uint64_t)nm + nseg;  // pieces: a table per message + the segments
   if (np > 0xffffffffull) return CPK_EINVAL;
   if (ctx->encoder == 0 || (ctx->encoder != 4 && np <= 1024)) {
@@ -714,7 +753,7 @@ int cpk_encode_batch_cap(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, u
   if (((uintptr_t)d_out & 15) || ((uintptr_t)d_in & 7)) return CPK_EINVAL;
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
+  if (n == 0) return hip_ok(fill_async(d_out_off, 0, 8, s));
   if (!sp_takes(ctx, n, max_seg_words))
     return e4_encode(ctx, d_in, d_swo, n, max_seg_words, d_out, d_out_off, s, false, out_cap);
   if (ctx->encoder == 0) {
@@ -743,7 +782,7 @@ int cpk_packed_size_batch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, 
   if ((uintptr_t)d_in & 7) return CPK_EINVAL;
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
+  if (n == 0) return hip_ok(fill_async(d_out_off, 0, 8, s));
   // a bound on the batch's 8192-word units (0: every piece is one): from the
   // hint, or from the batch's word count read back (synchronising the stream,
   // as cpk_encode_batch without a hint).  The chunk-parallel form is enqueued
@@ -753,7 +792,7 @@ int cpk_packed_size_batch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, 
   const bool can_chunk = ctx->size_form != 2 && ub <= (1ull << 25);
   uint64_t *sizes, *bsum;
   if (int rc = sizes_scratch(ctx, n, sizes, bsum)) return rc;
-  if (enc_tickets_reset(ctx, s) != hipSuccess || hipMemsetAsync(sizes, 0, (uint64_t)n * 8, s) != hipSuccess)
+  if (enc_tickets_reset(ctx, s) != hipSuccess || fill_async(sizes, 0, (uint64_t)n * 8, s) != hipSuccess)
     return CPK_EDEVICE;
   // the form, decided on the device from the piece sizes (no host sync, no
   // sample of the words)
@@ -781,7 +820,7 @@ int cpk_packed_size_messages(cpk_ctx ctx, const void *d_in, const uint64_t *d_sw
   if ((uintptr_t)d_in & 7) return CPK_EINVAL;
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
-  if (nm == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
+  if (nm == 0) return hip_ok(fill_async(d_out_off, 0, 8, s));
   const uint64_t np = (uint64_t)nm + nseg;  // pieces: a table per message + the segments
   if (np > 0xffffffffull) return CPK_EINVAL;
   MsgPass M;
@@ -842,7 +881,7 @@ int cpk_encode_batch_at(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, ui
           pgrp = c.take32(n);
         }))
       return rc;
-    if (hipMemsetAsync(pgrp, 0xff, (uint64_t)n * 4, s) != hipSuccess) return CPK_EDEVICE;
+    if (fill_async(pgrp, 0xff, (uint64_t)n * 4, s) != hipSuccess) return CPK_EDEVICE;
   }
   hipLaunchKernelGGL(cpk::at_prep_kernel, dim3(gg), dim3(tb), 0, s, A, d_grp_piece_off, ustart, pgrp, gfirst);
   A.pgrp = pgrp;
@@ -866,7 +905,7 @@ int cpk_ctx_take_error(cpk_ctx ctx, void *stream) {
   if (hipMemcpyAsync(&e, ctx->tickets + cpk::kTkErr, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
     return CPK_EDEVICE;
-  if (e && hipMemsetAsync(ctx->tickets + cpk::kTkErr, 0, 4, s) != hipSuccess) return CPK_EDEVICE;
+  if (e && fill_async(ctx->tickets + cpk::kTkErr, 0, 4, s) != hipSuccess) return CPK_EDEVICE;
   // kErrHint: a piece over its size hint; kErrWait: a cross-workgroup wait
   // timed out (cannot happen by design: every wave it waits on is resident);
   // kErrCap: packed bytes would have passed the caller's output capacity
@@ -1120,8 +1159,8 @@ int cpk_decode_message_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
   if (avail == 0) {
-    if ((d_msg_off && hipMemsetAsync(d_msg_off, 0, 8, s) != hipSuccess) ||
-        (d_msg_seg_off && hipMemsetAsync(d_msg_seg_off, 0, 8, s) != hipSuccess))
+    if ((d_msg_off && fill_async(d_msg_off, 0, 8, s) != hipSuccess) ||
+        (d_msg_seg_off && fill_async(d_msg_seg_off, 0, 8, s) != hipSuccess))
       return CPK_EDEVICE;
     return CPK_OK;
   }
@@ -1221,7 +1260,7 @@ static int unpacked_size_impl(cpk_ctx ctx, const void *d_packed, const uint64_t 
     return CPK_EINVAL;
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) return hip_ok(hipMemsetAsync(d_swo, 0, 8, s));
+  if (n == 0) return hip_ok(fill_async(d_swo, 0, 8, s));
   // words [n] | the scan's block sums | todo [n] (u32)
   uint64_t *words, *bsum;
   uint32_t *todo;
@@ -1260,7 +1299,7 @@ static int unpacked_size_impl(cpk_ctx ctx, const void *d_packed, const uint64_t 
     if (nbmax) {
       SsBufs B;
       if (int rc = ss_bufs(ctx, nbmax, B)) return rc;
-      if (hipMemsetAsync(todo, 0xff, (uint64_t)n * 4, s) != hipSuccess) return CPK_EDEVICE;
+      if (fill_async(todo, 0xff, (uint64_t)n * 4, s) != hipSuccess) return CPK_EDEVICE;
       for (uint32_t i = 0; i < n; ++i) {
         if (!takes(i)) continue;
         const uint64_t len = off[i + 1] - off[i], nb = (len + kSsBlock - 1) / kSsBlock;
@@ -1335,7 +1374,7 @@ int cpk_decode_batch_at(cpk_ctx ctx, const void *d_packed, uint64_t in_cap, cons
         }
       }))
     return rc;
-  if (hipMemsetAsync(psum, 0, 8, s) != hipSuccess || dec_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
+  if (fill_async(psum, 0, 8, s) != hipSuccess || dec_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
   DatArgs A = {d_src_off, d_src_len, d_grp_piece_off, d_seg_word_off, n,          ng,
                in_cap,    gbeg,      gend,            gout,           grouped ? 1u : 3u, d_grp_status};
   const unsigned gg = (ng + kDatThreads - 1) / kDatThreads;
@@ -1388,7 +1427,7 @@ int cpk_unpacked_size_batch_at(cpk_ctx ctx, const void *d_packed, uint64_t in_ca
     return CPK_EINVAL;
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) return hip_ok(hipMemsetAsync(d_seg_word_off, 0, 8, s));
+  if (n == 0) return hip_ok(fill_async(d_seg_word_off, 0, 8, s));
   // words [n] | the scan's block sums | begin | end [n] | todo [n] (u32)
   uint64_t *words, *bsum, *gbeg, *gend;
   uint32_t *todo;
@@ -1440,8 +1479,8 @@ int cpk_decode_messages_at(cpk_ctx ctx, const void *d_packed, uint64_t in_cap, c
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
   if (nm == 0) {
-    if (hipMemsetAsync(d_msg_seg_off, 0, 8, s) != hipSuccess) return CPK_EDEVICE;
-    return hip_ok(hipMemsetAsync(d_totals, 0, 8 * CPK_MAT_TOTALS, s));
+    if (fill_async(d_msg_seg_off, 0, 8, s) != hipSuccess) return CPK_EDEVICE;
+    return hip_ok(fill_async(d_totals, 0, 8 * CPK_MAT_TOTALS, s));
   }
   // the messages' words | first segment bytes | range ends | streams' ends [nm];
   // the words' scan | the decoders' piece ranges [nm + 1]; the two scans' block
@@ -1462,8 +1501,8 @@ int cpk_decode_messages_at(cpk_ctx ctx, const void *d_packed, uint64_t in_cap, c
         ohist = c.take32(kOrdClasses);
       }))
     return rc;
-  if (hipMemsetAsync(fit + kMatNoFit, 0xff, 8, s) != hipSuccess ||
-      hipMemsetAsync(fit + kMatCount, 0, 16, s) != hipSuccess)
+  if (fill_async(fit + kMatNoFit, 0xff, 8, s) != hipSuccess ||
+      fill_async(fit + kMatCount, 0, 16, s) != hipSuccess)
     return CPK_EDEVICE;
   const uint8_t *pk = (const uint8_t *)d_packed;
   const unsigned tg = (nm + kMatThreads - 1) / kMatThreads, tg1 = nm / kMatThreads + 1;
@@ -1518,8 +1557,8 @@ int cpk_encode_message_stream(cpk_ctx ctx, const void *d_in, uint64_t avail_word
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
   if (avail_words == 0) {
-    if ((d_out_off && hipMemsetAsync(d_out_off, 0, 8, s) != hipSuccess) ||
-        (d_msg_piece && hipMemsetAsync(d_msg_piece, 0, 8, s) != hipSuccess))
+    if ((d_out_off && fill_async(d_out_off, 0, 8, s) != hipSuccess) ||
+        (d_msg_piece && fill_async(d_msg_piece, 0, 8, s) != hipSuccess))
       return CPK_EDEVICE;
     return CPK_OK;
   }
@@ -1548,7 +1587,7 @@ int cpk_encode_message_stream(cpk_ctx ctx, const void *d_in, uint64_t avail_word
   h_info[4] = r[3];
   h_info[5] = r[4];
   const uint32_t n = (uint32_t)r[1];
-  if (n == 0) return hip_ok(hipMemsetAsync(d_out_off, 0, 8, s));
+  if (n == 0) return hip_ok(fill_async(d_out_off, 0, 8, s));
   // (every piece of a complete message is under 2^28 words and the tables
   // are not empty: the largest piece is a bound the batch call takes)
   if (int rc = cpk_encode_batch_cap(ctx, d_in, poff, n, r[4], d_out, out_cap, d_out_off, stream)) return rc;
@@ -1675,7 +1714,7 @@ int cpk_decode_messages(cpk_ctx ctx, const void *d_packed, const uint64_t *d_msg
   h_totals[0] = h_totals[1] = 0;
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
-  if (nm == 0) return hip_ok(hipMemsetAsync(d_msg_seg_off, 0, 8, s));
+  if (nm == 0) return hip_ok(fill_async(d_msg_seg_off, 0, 8, s));
   uint64_t *mwords, *mbeg, *mwoff, *bs0, *bs1;
   uint32_t *ord, *ohist;
   if (int rc = carve_reserve(ctx->status, 1024, [&](Carve &c) {

@@ -19,6 +19,23 @@
  * Calls on one context share its device workspace (counters, piece sizes,
  * step boundaries): issue them on one stream, or order the streams, so that
  * they do not run at the same time.
+ *
+ * Graph capture: a device entry point that makes no host synchronisation may
+ * be called on a stream that is being captured (hipStreamBeginCapture) and
+ * the graph replayed with other data in the same buffers: cpk_encode_batch,
+ * cpk_encode_batch_cap, cpk_encode_messages[_cap], cpk_packed_size_batch and
+ * cpk_encode_batch_at with max_seg_words != 0, cpk_packed_size_messages,
+ * cpk_decode_batch and cpk_unpacked_size_batch (their read-back for n <= 32
+ * is skipped while capturing), cpk_decode_batch_at,
+ * cpk_unpacked_size_batch_at, cpk_decode_messages_at, cpk_read_message,
+ * cpk_generate, cpk_count_mismatch, and cpk_decode_stream below 384 KiB of
+ * `avail` (from there on it reads its word total back).  The call must have
+ * run once uncaptured on the same context with the same n, counts, bounds and
+ * capacities: the context's buffers grow on demand, and growth allocates,
+ * which a capture does not allow.  Not to be captured: the calls documented
+ * to synchronise (cpk_decode_messages, the *_message_stream calls,
+ * cpk_ctx_take_error, cpk_ctx_dense_windows, every host form) and
+ * max_seg_words == 0.  tests/test_gpu_graph_replay.py replays each of them.
  */
 #ifndef CAPNP_PACKED_H
 #define CAPNP_PACKED_H
