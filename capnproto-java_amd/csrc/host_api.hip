@@ -86,10 +86,15 @@ __global__ void fill_kernel(uint8_t *p, uint32_t v4, uint64_t bytes) {
   for (uint64_t k = i; k < nw; k += step) reinterpret_cast<uint32_t *>(p)[k] = v4;
   if (i < (bytes & 3)) p[4 * nw + i] = (uint8_t)v4;
 }
-hipError_t fill_async(void *p, int value, size_t bytes, hipStream_t s) {
+// Whether work enqueued on `s` is being captured into a graph.  A status query
+// that fails is taken for a capture: what the callers do for one (a kernel for
+// a memset node, a clear ahead of the look-back, no read-back) is never wrong.
+bool stream_captured(hipStream_t s) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const bool captured = hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-  if (!captured || ((uintptr_t)p & 3) || bytes == 0) return hipMemsetAsync(p, value, bytes, s);
+  return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+hipError_t fill_async(void *p, int value, size_t bytes, hipStream_t s) {
+  if (!stream_captured(s) || ((uintptr_t)p & 3) || bytes == 0) return hipMemsetAsync(p, value, bytes, s);
   const uint64_t blocks = (bytes / 4 + 255) / 256;
   hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks > 1024 ? 1024 : blocks)), dim3(256), 0, s,
                      (uint8_t *)p, 0x01010101u * (uint32_t)(value & 0xff), (uint64_t)bytes);
@@ -108,6 +113,16 @@ struct DeviceGuard {
     if (cur != prev) hipSetDevice(prev);
   }
 };
+
+// `probe` of cpk_decode_batch and cpk_unpacked_size_batch: a batch of <= 32
+// pieces may read its extent back (one sync) to give a few large pieces a
+// faster path, never while the stream is being captured.  The host forms pass
+// false: they know the sizes, and their two-slot pipeline never blocks on it.
+bool may_probe(cpk_ctx ctx, uint32_t n, void *stream) {
+  if (n > 32 || !ctx) return false;
+  DeviceGuard g(ctx->device);
+  return !stream_captured((hipStream_t)stream);
+}
 
 // order[0..n) = 0..n-1 by size class, largest first (cpk::ord_*); hist:
 // kOrdClasses u32 of scratch
@@ -490,10 +505,8 @@ static int sp_plan(cpk_ctx ctx, const uint64_t *d_swo, const uint64_t *pdesc, ui
   // replay left would be valid for the next.  So a captured launch takes no
   // epoch from the counter: it is tagged kSpEpochCaptured, which no eager
   // launch ever draws (the counter runs 1..65535), and the clear of the words
-  // it polls is enqueued ahead of it, a node of the graph.  (A status query
-  // that fails is taken for a capture: the clear is never wrong.)
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const bool captured = hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+  // it polls is enqueued ahead of it, a node of the graph.
+  const bool captured = stream_captured(s);
   if (!captured && ++ctx->sp_epoch > 0xffffu) {
     ctx->sp_epoch = 1;
     fresh = true;
@@ -914,54 +927,66 @@ int cpk_ctx_take_error(cpk_ctx ctx, void *stream) {
   return (e & cpk::kErrWait) ? CPK_EDEVICE : (e & cpk::kErrCap) ? CPK_ENOMEM : CPK_EINVAL;
 }
 
-// one launch of the configured decoder (grid: as many workgroups per CU as
-// its LDS allows, at most 8; never more than the work needs)
+}  // extern "C"
+// ---- the decoders' launch layer ---------------------------------------------
 namespace {
 // which decoder a single-decoder call uses (the record-index one only when
 // forced: the by-density choice is made for batches, cpk_decode_batch)
 bool dec_v2(cpk_ctx ctx) { return ctx->decoder == 2; }
-
-// the context's choice, the block map, the record index, the block map's
-// dense form (decode_kernel<.., true>); the last three in the order of
-// dec_gate_kernel's skip words
+// the context's choice (dec_v2), the block map, the record index, the block
+// map's dense form (decode_kernel<.., true>); the last three in the order of
+// the gates' skip words (dec_gate_kernel, dat_gate_kernel) and of kDecForms
 enum DecKind { kDecCtx, kDecMap, kDecIndex, kDecDense };
+DecKind dec_ctx_kind(cpk_ctx ctx) { return dec_v2(ctx) ? kDecIndex : kDecMap; }
+// the shapes a decoder is launched in: batch, stream, batch on a range per piece (decode_at.hip)
+enum DecShape { kDecBatch, kDecStream, kDecAt };
 
-void dec_launch(cpk_ctx ctx, bool stream, unsigned want, const uint8_t *packed, uint64_t *in_off,
+// A decoder form, described here alone: its kernel for each shape (all take
+// the same arguments), its threads and its dynamic LDS.  A new form is a new
+// DecKind and its row here (and its word of the gates' skip words).
+struct DecForm {
+  void (*kernel[3])(const uint8_t *, uint64_t *, const uint64_t *, uint32_t, uint64_t *, int32_t *, uint32_t *,
+                    uint64_t, cpk::DecStreams);
+  unsigned threads;
+  uint32_t lds;
+};
+const DecForm kDecForms[] = {
+    {{cpk::decode_kernel<false>, cpk::decode_kernel<true>, cpk::decode_at_kernel<false>},
+     cpk::kDecThreads, cpk::kDecLds},
+    {{cpk::decode2_kernel<false>, cpk::decode2_kernel<true>, cpk::decode2_at_kernel}, cpk::kD2Threads, cpk::kD2Lds},
+    {{cpk::decode_kernel<false, true>, cpk::decode_kernel<true, true>, cpk::decode_at_kernel<true>},
+     cpk::kDecThreads, cpk::kDecLds}};
+
+// one launch of a decoder (grid: as many workgroups per CU as its LDS allows,
+// at most 8; never more than the work needs)
+void dec_launch(cpk_ctx ctx, DecShape shape, unsigned want, const uint8_t *packed, uint64_t *in_off,
                 const uint64_t *swo, uint32_t n, uint64_t *out, int32_t *status, uint64_t avail,
                 cpk::DecStreams sd, hipStream_t s, DecKind which = kDecCtx) {
-  const bool v2 = which == kDecCtx ? dec_v2(ctx) : which == kDecIndex;
-  const bool dense = which == kDecDense;
-  const uint32_t lds = v2 ? cpk::kD2Lds : cpk::kDecLds;
-  const unsigned per_cu = (unsigned)min(8u, 160u * 1024u / lds);
-  unsigned grid = per_cu * (unsigned)ctx->cus;
+  if (which == kDecCtx) which = dec_ctx_kind(ctx);
+  const DecForm &f = kDecForms[which - kDecMap];
+  unsigned grid = min(8u, 160u * 1024u / f.lds) * (unsigned)ctx->cus;
   if (grid > want) grid = want;
   if (grid == 0) grid = 1;
-  uint32_t *tk = ctx->tickets + cpk::kTkDec;
-  // (both decoders' kernels, every form, take the same arguments)
-  const auto kernel = v2      ? (stream ? cpk::decode2_kernel<true> : cpk::decode2_kernel<false>)
-                      : dense ? (stream ? cpk::decode_kernel<true, true> : cpk::decode_kernel<false, true>)
-                              : (stream ? cpk::decode_kernel<true> : cpk::decode_kernel<false>);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(v2 ? cpk::kD2Threads : cpk::kDecThreads), lds, s, packed, in_off, swo, n,
-                     out, status, tk, avail, sd);
+  hipLaunchKernelGGL(f.kernel[shape], dim3(grid), dim3(f.threads), f.lds, s, packed, in_off, swo, n, out, status,
+                     ctx->tickets + cpk::kTkDec, avail, sd);
+}
+
+// The forms a batch call enqueues.  By density (no CPK_DECODER) a gate kernel
+// writes dec_skip's three words and launch(kind, its word) runs for all three,
+// the ones not chosen return at once; a forced decoder alone, no skip word.
+bool dec_gated(cpk_ctx ctx) { return ctx->decoder == 3; }
+uint32_t *dec_skip(cpk_ctx ctx) { return ctx->tickets + cpk::kTkGate + cpk::kGateDecSkip; }
+template <class F>
+void dec_each_form(cpk_ctx ctx, F launch) {
+  if (!dec_gated(ctx)) return launch(dec_ctx_kind(ctx), (const uint32_t *)nullptr);
+  for (int k = kDecMap; k <= kDecDense; ++k) launch((DecKind)k, (const uint32_t *)dec_skip(ctx) + (k - kDecMap));
 }
 }  // namespace
+extern "C" {
 
-// probe: a batch of <= 32 pieces may read its extent back (one sync) to
-// decode a few large pieces as one stream.  The host forms pass false: they
-// know the sizes and take that path themselves (cpk_decode_host), so their
-// two-slot pipeline never blocks on it; nor does a stream being captured.
-
-int cpk_decode_batch(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off,
-                     const uint64_t *d_swo, uint32_t n, void *d_out, int32_t *d_status,
-                     void *stream) {
-  bool probe = n <= 32;
-  if (probe && ctx) {
-    DeviceGuard g(ctx->device);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
-      probe = false;
-  }
-  return decode_batch_impl(ctx, d_packed, d_in_off, d_swo, n, d_out, d_status, stream, probe);
+int cpk_decode_batch(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off, const uint64_t *d_swo, uint32_t n,
+                     void *d_out, int32_t *d_status, void *stream) {
+  return decode_batch_impl(ctx, d_packed, d_in_off, d_swo, n, d_out, d_status, stream, may_probe(ctx, n, stream));
 }
 
 static int decode_batch_impl(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off, const uint64_t *d_swo,
@@ -971,20 +996,15 @@ static int decode_batch_impl(cpk_ctx ctx, const void *d_packed, const uint64_t *
   if (n == 0) return CPK_OK;
   DeviceGuard g(ctx->device);
   hipStream_t s = (hipStream_t)stream;
-  if (dec_tickets_reset(ctx, s) != hipSuccess)
-    return CPK_EDEVICE;
+  if (dec_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
   // persistent: blocks of 4 independent waves, as many per CU as the LDS holds
   uint64_t *in_off = const_cast<uint64_t *>(d_in_off);
-  if (ctx->decoder != 3) {
-    dec_launch(ctx, false, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out,
-               d_status, 0, cpk::DecStreams::batch(), s);
-    return hip_ok(hipGetLastError());
-  }
-  // by density, decided on the device (dec_gate_kernel): all three enqueued,
-  // the ones not chosen return at their first instruction
-  uint32_t *skip = ctx->tickets + cpk::kTkGate + cpk::kGateDecSkip;  // [3]: kDecMap, kDecIndex, kDecDense
-  hipLaunchKernelGGL(cpk::dec_gate_kernel, dim3(1), dim3(64), 0, s, (const uint64_t *)d_in_off, d_swo, n, skip);
-  if (probe && n <= 32) {
+  // by density, decided on the device (a forced decoder: no gate, no probe)
+  const bool gate = dec_gated(ctx);
+  if (gate)
+    hipLaunchKernelGGL(cpk::dec_gate_kernel, dim3(1), dim3(64), 0, s, (const uint64_t *)d_in_off, d_swo, n,
+                       dec_skip(ctx));
+  if (gate && probe && n <= 32) {
     // A few pieces: read their extent back (one sync).  With >= 8 MiB of
     // words each on average the batch decoders would give a piece one wave
     // (one 64 MiB piece: ~100 ms), so decode them as one stream, 256-byte
@@ -1002,14 +1022,14 @@ static int decode_batch_impl(cpk_ctx ctx, const void *d_packed, const uint64_t *
                                  d_status, s);
       if (rc) return rc;
       hipLaunchKernelGGL(cpk::dec_stream_check_kernel, dim3(1), dim3(64), 0, s, (const uint64_t *)ctx->fl_buf.p,
-                         (const uint64_t *)d_in_off, (const int32_t *)d_status, n, skip);
-      if (dec_tickets_reset(ctx, s) != hipSuccess)
-        return CPK_EDEVICE;
+                         (const uint64_t *)d_in_off, (const int32_t *)d_status, n, dec_skip(ctx));
+      if (dec_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
     }
   }
-  for (int k = kDecMap; k <= kDecDense; ++k)
-    dec_launch(ctx, false, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out, d_status, 0,
-               cpk::DecStreams::batch(skip + (k - kDecMap)), s, (DecKind)k);
+  dec_each_form(ctx, [&](DecKind k, const uint32_t *sk) {
+    dec_launch(ctx, kDecBatch, (n + 3) / 4, (const uint8_t *)d_packed, in_off, d_swo, n, (uint64_t *)d_out, d_status, 0,
+               cpk::DecStreams::batch(sk), s, k);
+  });
   return hip_ok(hipGetLastError());
 }
 
@@ -1095,13 +1115,13 @@ int ss_decode(cpk_ctx ctx, const uint8_t *pk, uint64_t avail, uint64_t reach, co
   hipLaunchKernelGGL(ss_bound_kernel, dim3((n + 1 + 63) / 64), dim3(64), 0, s, pk, swo, n, nb, in_off, B);
   hipLaunchKernelGGL(ss_sub_kernel, dim3((unsigned)((nsub + 1 + tb - 1) / tb)), dim3(tb), 0, s, swo, n, nb,
                      (const uint64_t *)in_off, B);
-  dec_launch(ctx, false, (unsigned)((nsub + 3) / 4), pk, B.sin, B.sswo, (uint32_t)nsub, out, B.sst, 0,
+  dec_launch(ctx, kDecBatch, (unsigned)((nsub + 3) / 4), pk, B.sin, B.sswo, (uint32_t)nsub, out, B.sst, 0,
              DecStreams::batch(), s);
   hipLaunchKernelGGL(ss_check_kernel, dim3((unsigned)((nsub + tb - 1) / tb)), dim3(tb), 0, s, nsub, B);
   hipLaunchKernelGGL(ss_final_kernel, dim3((n + tb - 1) / tb), dim3(tb), 0, s, n, status, ctx->tickets + kTkDec, B,
                      getenv("CPK_STREAM_NO_FALLBACK") ? 1 : 0);
   // the one-wave decoder: no ticket unless the parallel path gave up
-  dec_launch(ctx, true, 1, pk, in_off, swo, n, out, status, avail, DecStreams::one(in_off + n), s);
+  dec_launch(ctx, kDecStream, 1, pk, in_off, swo, n, out, status, avail, DecStreams::one(in_off + n), s);
   return hip_ok(hipGetLastError());
 }
 }  // namespace
@@ -1134,7 +1154,7 @@ int cpk_decode_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
   if (dec_tickets_reset(ctx, s) != hipSuccess)
     return CPK_EDEVICE;
   // one stream: one wave works, the others find no ticket
-  dec_launch(ctx, true, 1, (const uint8_t *)d_packed, d_in_off, d_swo, n, (uint64_t *)d_out, d_status, avail,
+  dec_launch(ctx, kDecStream, 1, (const uint8_t *)d_packed, d_in_off, d_swo, n, (uint64_t *)d_out, d_status, avail,
              cpk::DecStreams::one(d_in_off + n), s);
   return hip_ok(hipGetLastError());
 }
@@ -1197,7 +1217,7 @@ int cpk_decode_message_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
   const uint64_t nsub = (nb + kSsSub - 1) / kSsSub;
   hipLaunchKernelGGL(ms_end_kernel, dim3(1), dim3(64), 0, s, pk, nb, out_cap_words, B, M);
   hipLaunchKernelGGL(ms_sub_kernel, dim3((unsigned)((nsub + 1 + tb - 1) / tb)), dim3(tb), 0, s, nb, B, M);
-  dec_launch(ctx, false, (unsigned)((nsub + 3) / 4), pk, B.sin, B.sswo, (uint32_t)nsub, (uint64_t *)d_out, B.sst, 0,
+  dec_launch(ctx, kDecBatch, (unsigned)((nsub + 3) / 4), pk, B.sin, B.sswo, (uint32_t)nsub, (uint64_t *)d_out, B.sst, 0,
              DecStreams::batch(), s);
   hipLaunchKernelGGL(ss_check_kernel, dim3((unsigned)((nsub + tb - 1) / tb)), dim3(tb), 0, s, nsub, B);
   uint64_t r[8];
@@ -1252,6 +1272,17 @@ int cpk_decode_message_stream(cpk_ctx ctx, const void *d_packed, uint64_t avail,
 // one after the other while their waves would run side by side, so a piece
 // of a batch of n takes the map from n * kUsBlockMin bytes.
 constexpr uint64_t kUsBlockMin = 64 * 1024;
+// The wave form: persistent workgroups of 4 independent waves, kUsWpe per CU.
+// end: the ranges are beg[i] .. end[i] (us_wave_at_kernel); null: beg holds n + 1 offsets.
+static void us_wave_launch(cpk_ctx ctx, const uint8_t *pk, const uint64_t *beg, const uint64_t *end, uint32_t n,
+                           uint64_t *words, int32_t *status, const uint32_t *todo, hipStream_t s) {
+  using namespace cpk;
+  const unsigned want = (n + 3) / 4, full = (unsigned)(kUsWpe * ctx->cus);
+  const dim3 grid(want < full ? want : full), block(kUsThreads);
+  uint32_t *tk = ctx->tickets + kTkDec;
+  if (end) hipLaunchKernelGGL(us_wave_at_kernel, grid, block, kUsLds, s, pk, beg, end, n, words, status, tk, todo);
+  else hipLaunchKernelGGL(us_wave_kernel, grid, block, kUsLds, s, pk, beg, n, words, status, tk, todo);
+}
 static int unpacked_size_impl(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off, uint32_t n,
                               uint64_t *d_swo, int32_t *d_status, void *stream, bool probe, const uint64_t *h_off) {
   using namespace cpk;
@@ -1311,26 +1342,16 @@ static int unpacked_size_impl(cpk_ctx ctx, const void *d_packed, const uint64_t 
     }
   }
   if (dec_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
-  // persistent: workgroups of 4 independent waves, kUsWpe per CU
-  const unsigned want = (n + 3) / 4, full = (unsigned)(kUsWpe * ctx->cus);
-  hipLaunchKernelGGL(us_wave_kernel, dim3(want < full ? want : full), dim3(kUsThreads), kUsLds, s, pk, d_in_off, n,
-                     words, d_status, ctx->tickets + kTkDec, mapped ? (const uint32_t *)todo : (const uint32_t *)nullptr);
+  us_wave_launch(ctx, pk, d_in_off, nullptr, n, words, d_status, mapped ? todo : nullptr, s);
   scan_launch(words, n, bsum, d_swo, s);
   return hip_ok(hipGetLastError());
 }
 
 int cpk_unpacked_size_batch(cpk_ctx ctx, const void *d_packed, const uint64_t *d_in_off, uint32_t n,
                             uint64_t *d_seg_word_off, int32_t *d_status, void *stream) {
-  // (a batch of <= 32 pieces may read its extent back, as cpk_decode_batch
-  // does; not while the stream is being captured)
-  bool probe = n <= 32 && n > 0;
-  if (probe && ctx) {
-    DeviceGuard g(ctx->device);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
-      probe = false;
-  }
-  return unpacked_size_impl(ctx, d_packed, d_in_off, n, d_seg_word_off, d_status, stream, probe, nullptr);
+  // (a batch of <= 32 pieces may read its extent back, as cpk_decode_batch does)
+  return unpacked_size_impl(ctx, d_packed, d_in_off, n, d_seg_word_off, d_status, stream,
+                            n > 0 && may_probe(ctx, n, stream), nullptr);
 }
 
 // ---- decode from caller-given ranges (decode_at.hip) -------------------------
@@ -1382,34 +1403,19 @@ int cpk_decode_batch_at(cpk_ctx ctx, const void *d_packed, uint64_t in_cap, cons
                      (uint64_t *)nullptr, (uint32_t *)nullptr);
   if (n) {
     const uint8_t *pk = (const uint8_t *)d_packed;
-    uint32_t *skip = ctx->tickets + kTkGate + kGateDecSkip;  // [3]: kDecMap, kDecIndex, kDecDense
-    const bool gate = ctx->decoder == 3;
-    if (gate)
+    if (dec_gated(ctx))
       hipLaunchKernelGGL(dat_gate_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long *)psum, d_seg_word_off,
-                         n, skip);
+                         n, dec_skip(ctx));
     if (grouped) ord_launch(glen, ng, ohist, ord, s);
-    // one form of the batch decoders on a range per piece
-    auto piece_launch = [&](DecKind k, const uint32_t *sk) {
-      const bool v2 = k == kDecIndex;
-      const uint32_t lds = v2 ? kD2Lds : kDecLds;
-      unsigned grid = (unsigned)min(8u, 160u * 1024u / lds) * (unsigned)ctx->cus;
-      if (grid > (n + 3) / 4) grid = (n + 3) / 4;
-      const auto kernel = v2 ? decode2_at_kernel : k == kDecDense ? decode_at_kernel<true> : decode_at_kernel<false>;
-      hipLaunchKernelGGL(kernel, dim3(grid), dim3(v2 ? kD2Threads : kDecThreads), lds, s, pk, gbeg, d_seg_word_off, n,
-                         (uint64_t *)d_out, d_status, ctx->tickets + kTkDec, (uint64_t)0,
-                         DecStreams::batch(sk));
-    };
-    // (every form enqueued for the device to choose, the ones not picked
-    // return at once; a forced decoder alone, as decode_batch_impl)
-    for (int k = kDecMap; k <= kDecDense; ++k) {
-      if (!gate && k != (dec_v2(ctx) ? kDecIndex : kDecMap)) continue;
-      const uint32_t *sk = gate ? skip + (k - kDecMap) : nullptr;
+    // groups: the stream forms; none: the batch forms on a range per piece
+    dec_each_form(ctx, [&](DecKind k, const uint32_t *sk) {
       if (grouped)
-        dec_launch(ctx, true, (ng + 3) / 4, pk, pin, d_seg_word_off, n, (uint64_t *)d_out, d_status, 0,
-                   DecStreams{gbeg, gend, d_grp_piece_off, ng, gout, sk, ord}, s, (DecKind)k);
+        dec_launch(ctx, kDecStream, (ng + 3) / 4, pk, pin, d_seg_word_off, n, (uint64_t *)d_out, d_status, 0,
+                   DecStreams{gbeg, gend, d_grp_piece_off, ng, gout, sk, ord}, s, k);
       else
-        piece_launch((DecKind)k, sk);
-    }
+        dec_launch(ctx, kDecAt, (n + 3) / 4, pk, gbeg, d_seg_word_off, n, (uint64_t *)d_out, d_status, (uint64_t)0,
+                   DecStreams::batch(sk), s, k);
+    });
   }
   hipLaunchKernelGGL(dat_final_kernel, dim3(gg), dim3(kDatThreads), 0, s, A, d_status, d_grp_used);
   return hip_ok(hipGetLastError());
@@ -1443,10 +1449,7 @@ int cpk_unpacked_size_batch_at(cpk_ctx ctx, const void *d_packed, uint64_t in_ca
   DatArgs A = {d_src_off, d_src_len, nullptr, nullptr, n, n, in_cap, gbeg, gend, nullptr, 1u, d_status};
   hipLaunchKernelGGL(dat_prep_kernel, dim3((n + kDatThreads - 1) / kDatThreads), dim3(kDatThreads), 0, s, A,
                      (unsigned long long *)nullptr, (uint64_t *)nullptr, words, todo);
-  const unsigned want = (n + 3) / 4, full = (unsigned)(kUsWpe * ctx->cus);
-  hipLaunchKernelGGL(us_wave_at_kernel, dim3(want < full ? want : full), dim3(kUsThreads), kUsLds, s,
-                     (const uint8_t *)d_packed, (const uint64_t *)gbeg, (const uint64_t *)gend, n, words, d_status,
-                     ctx->tickets + kTkDec, (const uint32_t *)todo);
+  us_wave_launch(ctx, (const uint8_t *)d_packed, gbeg, gend, n, words, d_status, todo, s);
   scan_launch(words, n, bsum, d_seg_word_off, s);
   return hip_ok(hipGetLastError());
 }
@@ -1521,19 +1524,14 @@ int cpk_decode_messages_at(cpk_ctx ctx, const void *d_packed, uint64_t in_cap, c
   // (no room for a segment: no message fits, there is nothing to decode)
   if (seg_cap) {
     if (dec_tickets_reset(ctx, s) != hipSuccess) return CPK_EDEVICE;
-    uint32_t *skip = ctx->tickets + kTkGate + kGateDecSkip;  // [3]: kDecMap, kDecIndex, kDecDense
-    const bool gate = ctx->decoder == 3;
-    if (gate)
+    if (dec_gated(ctx))
       hipLaunchKernelGGL(dat_gate_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long *)(fit + kMatBytes),
-                         (const uint64_t *)(fit + kMatGate), 1u, skip);
+                         (const uint64_t *)(fit + kMatGate), 1u, dec_skip(ctx));
     ord_launch(mwords, nm, ohist, ord, s);
-    // (every form enqueued for the device to choose, a forced decoder alone, as
-    // cpk_decode_batch_at)
-    for (int k = kDecMap; k <= kDecDense; ++k) {
-      if (!gate && k != (dec_v2(ctx) ? kDecIndex : kDecMap)) continue;
-      dec_launch(ctx, true, (nm + 3) / 4, pk, d_seg_in_off, d_seg_word_off, seg_cap, (uint64_t *)d_out, d_seg_status, 0,
-                 DecStreams{mbeg, mend, spc, nm, mout, gate ? skip + (k - kDecMap) : nullptr, ord}, s, (DecKind)k);
-    }
+    dec_each_form(ctx, [&](DecKind k, const uint32_t *sk) {
+      dec_launch(ctx, kDecStream, (nm + 3) / 4, pk, d_seg_in_off, d_seg_word_off, seg_cap, (uint64_t *)d_out,
+                 d_seg_status, 0, DecStreams{mbeg, mend, spc, nm, mout, sk, ord}, s, k);
+    });
   }
   hipLaunchKernelGGL(mat_final_kernel, dim3(tg), dim3(kMatThreads), 0, s, nm, d_src_off, d_src_len,
                      (const uint64_t *)spc, (const uint64_t *)mout, (const int32_t *)d_seg_status, d_msg_status,
@@ -1691,7 +1689,7 @@ static int read_message_impl(cpk_ctx ctx, const void *d_packed, uint64_t avail, 
     // one wave over the table's pieces and the segments (the piece count is
     // on the device: a one-stream descriptor), none of the padding; its
     // tickets were zeroed by rm_table_kernel
-    dec_launch(ctx, true, 1, (const uint8_t *)d_packed, in_off, swo, kRmPieces, (uint64_t *)d_out, pst, avail,
+    dec_launch(ctx, kDecStream, 1, (const uint8_t *)d_packed, in_off, swo, kRmPieces, (uint64_t *)d_out, pst, avail,
                cpk::DecStreams::one_desc(sdesc, send_out), s);
     rc = hip_ok(hipGetLastError());
   }
@@ -1763,7 +1761,7 @@ int cpk_decode_messages(cpk_ctx ctx, const void *d_packed, const uint64_t *d_msg
     // registers -- with 36 B/lane of spills it had been 49.9,
     // profiles/r5aa_stream_sgpr.txt)
     const bool dense = ctx->decoder == 3 && pk[1] >= pk[0] && 100 * (pk[1] - pk[0]) >= 80 * 8 * h_totals[0];
-    dec_launch(ctx, true, (nm + 3) / 4, (const uint8_t *)d_packed, d_seg_in_off, (const uint64_t *)d_seg_word_off,
+    dec_launch(ctx, kDecStream, (nm + 3) / 4, (const uint8_t *)d_packed, d_seg_in_off, (const uint64_t *)d_seg_word_off,
                (uint32_t)h_totals[1], (uint64_t *)d_out, d_seg_status, 0,
                cpk::DecStreams::many(mbeg, d_msg_off + 1, d_msg_seg_off, nm, mwords, ord), s,
                dense ? kDecDense : kDecCtx);
