@@ -46,6 +46,7 @@ EXPORTS = [
     "cpk_encode_batch_at",
     "cpk_decode_batch_at", "cpk_unpacked_size_batch_at",
     "cpk_decode_messages_at",
+    "cpk_encode_messages_at",
 ]
 MAT_TOTALS = 3  # CPK_MAT_TOTALS
 MSG_HEAD_WORDS, MSG_INFO_WORDS = 257, 517  # CPK_MSG_HEAD_WORDS, CPK_MSG_INFO_WORDS
@@ -132,6 +133,7 @@ def load(path: Path | None = None, strict: bool = True) -> ctypes.CDLL:
         "cpk_decode_batch_at": ([vp, vp, u64, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp], i32),
         "cpk_unpacked_size_batch_at": ([vp, vp, u64, vp, vp, u32, vp, vp, vp], i32),
         "cpk_decode_messages_at": ([vp, vp, u64, vp, vp, u32, u64, vp, u64, vp, vp, vp, u32, vp, vp, vp, vp, vp], i32),
+        "cpk_encode_messages_at": ([vp, vp, vp, u32, vp, u32, u64, vp, u64, vp, vp, vp, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         if not strict and not hasattr(L, name):
@@ -800,7 +802,31 @@ def _decode_messages_at(self, d_packed, in_cap: int, d_src_off, d_src_len, d_out
     _check(rc, "cpk_decode_messages_at")
 
 
+def _encode_messages_at(self, d_in, d_seg_word_off, d_msg_seg_off, max_seg_words: int, d_out, out_cap: int,
+                        d_dst_off, d_dst_cap, d_piece_off, d_msg_len, d_status, stream=None, nm=None, nseg=None):
+    """cpk_encode_messages_at: SerializePacked.write of message m (segments
+    d_msg_seg_off[m] .. [m+1], its table built on the device) to d_out +
+    d_dst_off[m], into a slot of d_dst_cap[m] bytes (None: to out_cap).
+    max_seg_words is required.  Written: d_piece_off[nm + nseg] (message order:
+    table, segments), d_msg_len[nm], d_status[nm] (OK, ENOMEM for a slot too
+    small or past out_cap, EINVAL for a segment over max_seg_words); no byte of
+    d_out outside the messages' packed bytes is touched.  d_dst_off / d_msg_len
+    are decode_messages_at's d_src_off / d_src_len.  Never synchronises.  nm,
+    nseg: the counts when they are not the offset arrays'."""
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    if nseg is None:
+        nseg = d_seg_word_off.numel() - 1 if d_seg_word_off is not None else 0
+    if nm is None:
+        nm = d_msg_seg_off.numel() - 1 if d_msg_seg_off is not None else 0
+    rc = self._lib.cpk_encode_messages_at(self.handle, ptr(d_in), ptr(d_seg_word_off), int(nseg),
+                                          ptr(d_msg_seg_off), int(nm), int(max_seg_words), ptr(d_out), int(out_cap),
+                                          ptr(d_dst_off), ptr(d_dst_cap), ptr(d_piece_off), ptr(d_msg_len),
+                                          ptr(d_status), self._stream(stream))
+    _check(rc, "cpk_encode_messages_at")
+
+
 Context.encode_batch_at = _encode_batch_at
+Context.encode_messages_at = _encode_messages_at
 Context.decode_batch_at = _decode_batch_at
 Context.decode_messages_at = _decode_messages_at
 Context.unpacked_size_batch_at = _unpacked_size_batch_at

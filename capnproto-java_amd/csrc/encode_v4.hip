@@ -551,11 +551,11 @@ __device__ __forceinline__ void e4_emit_step(uint64_t word, bool valid, uint64_t
   }
 }
 
-__global__ __launch_bounds__(kE4Threads, kE4Wpe) void e4_emit_kernel(
+template <bool kEnds = false> __global__ __launch_bounds__(kE4Threads, kE4Wpe) void e4_emit_kernel(
     const uint64_t *__restrict__ in, const uint64_t *__restrict__ swo, uint32_t n,
     const uint64_t *__restrict__ out_off, uint8_t *__restrict__ out, uint32_t *ticket,
-    const uint64_t *__restrict__ bvbuf, uint64_t stride, const uint32_t *skip,
-    const uint64_t *__restrict__ sizes, uint64_t ocap, uint32_t *err, const uint32_t *order) {
+    const uint64_t *__restrict__ bvbuf, uint64_t stride, const uint32_t *skip, const uint64_t *__restrict__ sizes,
+    std::conditional_t<kEnds, const uint64_t *, uint64_t> ocap, uint32_t *err, const uint32_t *order) {
   if (skip && __builtin_amdgcn_readfirstlane(*skip)) return;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const uint64_t *lut = reinterpret_cast<const uint64_t *>(smem + kE4oLut);
@@ -577,9 +577,9 @@ __global__ __launch_bounds__(kE4Threads, kE4Wpe) void e4_emit_kernel(
     const uint64_t *src = in + w0;
     const uint64_t obase = out_off[seg];
     // a piece whose bytes would pass the caller's capacity is not written
-    // (ArrayOutputStream.java:40-42 refuses such a write); reported
-    if (obase + sizes[seg] > ocap) {
-      if (lane == 0) atomicOr(err, kErrCap);
+    // (ArrayOutputStream.java:40-42 refuses such a write); reported (kEnds: its slot's end, ocap[seg]; unreported)
+    if (obase + sizes[seg] > [&] { if constexpr (kEnds) return ocap[seg]; else return ocap; }()) {
+      if (!kEnds && lane == 0) atomicOr(err, kErrCap);
       continue;
     }
     uint64_t rpos = obase, fl = obase >> 4;

@@ -44,6 +44,8 @@ struct cpk_ctx_s {
   int usize_form;         // cpk_unpacked_size_batch: 0 by piece size, 1 block map, 2 wave per piece (CPK_USIZE_FORM)
   int at_form;            // cpk_encode_batch_at: 0 by density, 1 dense, 2 sparse (CPK_AT_FORM)
   DevBuf at_buf;          // cpk_encode_batch_at with groups: the groups' first units [ng + 1] | the pieces' groups [n]
+  int msg_at_form;        // cpk_encode_messages_at: 0 by segment size, 1 wave, 2 placed (CPK_MSG_AT_FORM)
+  DevBuf mat_buf;         // cpk_encode_messages_at: what its two forms pass between their kernels (mat_scratch)
   // CPK_HOST_TRACE=1 (read at creation): host wall time of the one-message
   // host paths (cpk_encode_host[_gather], cpk_read_message_host) by phase,
   // summed per context and printed to stderr by cpk_ctx_destroy
@@ -349,6 +351,9 @@ int cpk_ctx_create(int device, cpk_ctx *out) {
     // CPK_AT_FORM=dense / sparse forces the placed encoder's form (A/B of its gate)
     const char *a = getenv("CPK_AT_FORM");
     c->at_form = (a && a[0] == 'd') ? 1 : (a && a[0] == 's') ? 2 : 0;
+    // CPK_MSG_AT_FORM=wave / place forces cpk_encode_messages_at's form (A/B of its gate)
+    const char *ma = getenv("CPK_MSG_AT_FORM");
+    c->msg_at_form = (ma && ma[0] == 'w') ? 1 : (ma && ma[0] == 'p') ? 2 : 0;
   }
   if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
     c->cus = 256;
@@ -403,7 +408,7 @@ void cpk_ctx_destroy(cpk_ctx ctx) {
   }
   // (every DevBuf member: a new one is added here)
   for (DevBuf *b : {&ctx->status, &ctx->sp_status, &ctx->sp_desc, &ctx->sp_units, &ctx->e4_bv, &ctx->ss_buf,
-                    &ctx->ms_buf, &ctx->ems_buf, &ctx->rm_buf, &ctx->fl_buf, &ctx->rm_copy, &ctx->at_buf})
+                    &ctx->ms_buf, &ctx->ems_buf, &ctx->rm_buf, &ctx->fl_buf, &ctx->rm_copy, &ctx->at_buf, &ctx->mat_buf})
     if (b->p) hipFree(b->p);
   if (ctx->tickets) hipFree(ctx->tickets);
   if (ctx->probe_pin) hipHostFree(ctx->probe_pin);
@@ -594,22 +599,30 @@ static int e4_rows(cpk_ctx ctx, const uint64_t *d_swo, uint32_t n, uint64_t hint
 // The two passes' kernels, each launched from here alone.  rows: whether the
 // size pass keeps its boundary rows (e4_rows, `stride`) for an emit pass;
 // skip: a device gate's word (nonzero: the other form took the batch), or
-// null; order: the pieces largest first, or null.
+// null; order: the pieces largest first, or null; err: where a piece over the
+// hint is reported, null: the context's error word (cpk_ctx_take_error).
 static void e4_size_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, uint64_t hint,
                            uint64_t *sizes, bool rows, uint64_t stride, const uint32_t *skip,
-                           const uint32_t *order, hipStream_t s) {
+                           const uint32_t *order, hipStream_t s, uint32_t *err = nullptr) {
   hipLaunchKernelGGL(rows ? cpk::e4_size_kernel<true> : cpk::e4_size_kernel<false>, dim3(e4_grid(ctx, n)),
                      dim3(cpk::kE4Threads), 0, s, (const uint64_t *)d_in, d_swo, n, sizes,
-                     ctx->tickets + cpk::kTkEnc, hint, ctx->tickets + cpk::kTkErr,
+                     ctx->tickets + cpk::kTkEnc, hint, err ? err : ctx->tickets + cpk::kTkErr,
                      rows ? ctx->e4_bv.p : (uint64_t *)nullptr, rows ? stride : (uint64_t)0, skip, order);
 }
-// (off: the pieces' output offsets; sizes: the size pass's)
+// (off: the pieces' output offsets; sizes: the size pass's; ends: an end per
+// piece in place of out_cap, a piece past its own skipped without a report)
 static void e4_emit_launch(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, const uint64_t *off,
                            const uint64_t *sizes, uint64_t stride, const uint32_t *skip, const uint32_t *order,
-                           void *d_out, uint64_t out_cap, hipStream_t s) {
-  hipLaunchKernelGGL(cpk::e4_emit_kernel, dim3(e4_grid(ctx, n)), dim3(cpk::kE4Threads), cpk::kE4Lds, s,
-                     (const uint64_t *)d_in, d_swo, n, off, (uint8_t *)d_out, ctx->tickets + cpk::kTkDec,
-                     (const uint64_t *)ctx->e4_bv.p, stride, skip, sizes, out_cap, ctx->tickets + cpk::kTkErr, order);
+                           void *d_out, uint64_t out_cap, hipStream_t s, const uint64_t *ends = nullptr) {
+  auto launch = [&](auto kernel, auto cap) {
+    hipLaunchKernelGGL(kernel, dim3(e4_grid(ctx, n)), dim3(cpk::kE4Threads), cpk::kE4Lds, s, (const uint64_t *)d_in,
+                       d_swo, n, off, (uint8_t *)d_out, ctx->tickets + cpk::kTkDec, (const uint64_t *)ctx->e4_bv.p,
+                       stride, skip, sizes, cap, ctx->tickets + cpk::kTkErr, order);
+  };
+  if (ends)
+    launch(cpk::e4_emit_kernel<true>, ends);
+  else
+    launch(cpk::e4_emit_kernel<false>, out_cap);
 }
 
 // Arms a device gate over the piece sizes (e4_gate_kernel, sz_gate_kernel):
@@ -663,7 +676,8 @@ int e4_encode(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, 
 // segments' output offsets get room.  Segments are taken largest first (a
 // wave takes a whole segment, and a 256 KiB one taken last kept the rest of
 // the chip idle behind it): by CPK_E4_ORDER=1 in both passes, =2 in the emit
-// pass only.
+// pass only.  d_out_off null: the pieces' sizes alone, no offsets (the caller
+// places the messages itself); skip, err: as e4_size_launch takes them.
 struct MsgPass {
   uint64_t *ssize, *tsize;  // the segments' and the tables' packed sizes
   uint64_t *soff;           // the segments' output offsets, for msg_table_emit_kernel to write (rows only)
@@ -672,7 +686,7 @@ struct MsgPass {
 };
 static int msg_front(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t nseg,
                      const uint64_t *d_msg_seg_off, uint32_t nm, uint64_t hint, uint64_t *d_out_off, hipStream_t s,
-                     bool rows, MsgPass &M) {
+                     bool rows, MsgPass &M, const uint32_t *skip = nullptr, uint32_t *err = nullptr) {
   const uint64_t np = (uint64_t)nm + nseg;
   uint64_t *comb, *bsum;
   uint32_t *sord, *shist;
@@ -700,11 +714,12 @@ static int msg_front(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint3
     M.order = sord;
   }
   if (nseg)
-    e4_size_launch(ctx, d_in, d_swo, nseg, hint, M.ssize, rows, M.stride, nullptr,
-                   ctx->e4_order == 1 ? M.order : nullptr, s);
+    e4_size_launch(ctx, d_in, d_swo, nseg, hint, M.ssize, rows, M.stride, skip,
+                   ctx->e4_order == 1 ? M.order : nullptr, s, err);
   // the tables, sized as msg_table_emit_kernel builds them
   const unsigned tb = 256, tg = (nm + tb - 1) / tb;
   hipLaunchKernelGGL(cpk::msg_table_size_kernel, dim3(tg), dim3(tb), 0, s, d_swo, d_msg_seg_off, nm, M.tsize);
+  if (!d_out_off) return CPK_OK;
   hipLaunchKernelGGL(cpk::msg_interleave_kernel, dim3(tg), dim3(tb), 0, s, d_msg_seg_off, nm,
                      (const uint64_t *)M.tsize, (const uint64_t *)M.ssize, comb);
   scan_launch(comb, (uint32_t)np, bsum, d_out_off, s);
@@ -841,10 +856,46 @@ int cpk_packed_size_messages(cpk_ctx ctx, const void *d_in, const uint64_t *d_sw
   return hip_ok(hipGetLastError());
 }
 
-// ---- encode to caller-given offsets (encode_at.hip) -------------------------
-// The single pass's plan (sp_plan: units, status words, epoch), the piece ->
-// group map (at_prep_kernel) and both forms of sp_place_kernel, enqueued for
-// the device to choose (at_gate_kernel over e4_minmax_kernel's sample).
+// ---- encode to caller-given offsets (encode_at.hip, encode_msg_at.hip) ------
+// The placed single pass over A's pieces and groups: the single pass's plan
+// (sp_plan: units, status words, epoch; ub: sp_unit_bound's units), the piece
+// -> group map (at_prep_kernel) and both forms of sp_place_kernel, enqueued for
+// the device to choose: tickets[kTkGate + kGateSparse] names the one that runs
+// (0 dense, 1 sparse), left there by the caller's gate (at_gate_kernel over
+// e4_minmax_kernel's sample), which has been enqueued.
+static int at_place_launch(cpk_ctx ctx, cpk::AtArgs A, const uint64_t *d_grp_piece_off, uint64_t max_seg_words,
+                           uint64_t ub, hipStream_t s) {
+  const uint32_t n = A.n, ng = A.ng;
+  const uint64_t *d_swo = A.swo;
+  const unsigned tb = 256, gg = (ng + tb - 1) / tb;
+  SpPlan P;
+  if (int rc = sp_plan(ctx, d_swo, nullptr, n, max_seg_words, ub, s, P)) return rc;
+  // (the pieces' first units: the scan the unit table was filled from)
+  const uint64_t *ustart = P.nunits ? P.nunits - n : nullptr;
+  uint64_t *gfirst = nullptr;
+  uint32_t *pgrp = nullptr;
+  if (d_grp_piece_off) {
+    if (int rc = carve_reserve(ctx->at_buf, 1024, [&](Carve &c) {
+          gfirst = c.take((uint64_t)ng + 1);
+          pgrp = c.take32(n);
+        }))
+      return rc;
+    if (fill_async(pgrp, 0xff, (uint64_t)n * 4, s) != hipSuccess) return CPK_EDEVICE;
+  }
+  hipLaunchKernelGGL(cpk::at_prep_kernel, dim3(gg), dim3(tb), 0, s, A, d_grp_piece_off, ustart, pgrp, gfirst);
+  A.pgrp = pgrp;
+  A.gfirst = d_grp_piece_off ? gfirst : ustart;  // (a piece its own group: its first unit)
+  const uint32_t *pick = ctx->tickets + cpk::kTkGate + cpk::kGateSparse;
+  auto launch = [&](auto kernel, int wpe, uint32_t lds, uint32_t form) {
+    hipLaunchKernelGGL(kernel, dim3(sp_grid(ctx, wpe, P)), dim3(cpk::kSpThreads), lds, s, A, P.status, P.epoch,
+                       ctx->tickets + cpk::kTkPlan, P.utab, P.nunits, P.ustate, max_seg_words,
+                       ctx->tickets + cpk::kTkErr, pick, form);
+  };
+  launch(cpk::sp_place_kernel<cpk::SpDense>, cpk::SpDense::kWpe, cpk::SpLay<cpk::SpDense>::kLds, 0u);
+  launch(cpk::sp_place_kernel<cpk::SpSparse>, cpk::SpSparse::kWpe, cpk::SpLay<cpk::SpSparse>::kLds, 1u);
+  return hip_ok(hipGetLastError());
+}
+
 int cpk_encode_batch_at(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t n, uint64_t max_seg_words,
                         const uint64_t *d_grp_piece_off, uint32_t ng, void *d_out, uint64_t out_cap,
                         const uint64_t *d_dst_off, const uint64_t *d_dst_cap, uint64_t *d_piece_off,
@@ -882,31 +933,102 @@ int cpk_encode_batch_at(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, ui
   uint32_t samples;
   if (int rc = gate_arm(ctx, d_swo, n, true, d_in, s, samples)) return rc;
   hipLaunchKernelGGL(cpk::at_gate_kernel, dim3(1), dim3(64), 0, s, ctx->tickets, samples, (uint32_t)ctx->at_form);
-  SpPlan P;
-  if (int rc = sp_plan(ctx, d_swo, nullptr, n, max_seg_words, ub, s, P)) return rc;
-  // (the pieces' first units: the scan the unit table was filled from)
-  const uint64_t *ustart = P.nunits ? P.nunits - n : nullptr;
-  uint64_t *gfirst = nullptr;
-  uint32_t *pgrp = nullptr;
-  if (d_grp_piece_off) {
-    if (int rc = carve_reserve(ctx->at_buf, 1024, [&](Carve &c) {
-          gfirst = c.take((uint64_t)ng + 1);
-          pgrp = c.take32(n);
-        }))
-      return rc;
-    if (fill_async(pgrp, 0xff, (uint64_t)n * 4, s) != hipSuccess) return CPK_EDEVICE;
+  return at_place_launch(ctx, A, d_grp_piece_off, max_seg_words, ub, s);
+}
+
+int cpk_encode_messages_at(cpk_ctx ctx, const void *d_in, const uint64_t *d_swo, uint32_t nseg,
+                           const uint64_t *d_msg_seg_off, uint32_t nm, uint64_t max_seg_words, void *d_out,
+                           uint64_t out_cap, const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
+                           uint64_t *d_piece_off, uint64_t *d_msg_len, int32_t *d_status, void *stream) {
+  using namespace cpk;
+  if (!ctx || max_seg_words == 0 || (nseg && !d_swo)) return CPK_EINVAL;
+  if (nm && (!d_msg_seg_off || !d_out || !d_dst_off || !d_piece_off || !d_msg_len || !d_status)) return CPK_EINVAL;
+  if (((uintptr_t)d_out & 15) || ((uintptr_t)d_in & 7) || ((uintptr_t)d_status & 3)) return CPK_EINVAL;
+  for (const void *q : {(const void *)d_swo, (const void *)d_msg_seg_off, (const void *)d_dst_off,
+                        (const void *)d_dst_cap, (const void *)d_piece_off, (const void *)d_msg_len})
+    if ((uintptr_t)q & 7) return CPK_EINVAL;
+  if (nm == 0) return CPK_OK;
+  if ((uint64_t)nm + nseg > 0xffffffffull) return CPK_EINVAL;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (out_cap > (1ull << 62)) out_cap = 1ull << 62;  // (as cpk_encode_batch_at: no byte address wraps)
+  // (a segment of 2^31 words or more is refused whatever the bound: a larger
+  // bound says no more, and none of the arithmetic below wraps)
+  if (max_seg_words >= (1ull << 31)) max_seg_words = (1ull << 31) - 1;
+  // What can run, known without a read-back: the two passes when the size
+  // pass's rows at max_seg_words stay within their 4 GiB, the placed single
+  // pass when its unit table stays within 2^25 entries.  A forced form
+  // (CPK_MSG_AT_FORM) is enqueued alone where it can run.
+  const bool rows_fit = (max_seg_words + 63) / 64 <= kE4MaxRows / (nseg ? nseg : 1);
+  const uint64_t ub = sp_unit_bound(nseg, max_seg_words);
+  const bool units_fit = nseg && ub <= (1ull << 25);
+  if (!rows_fit && !units_fit) return CPK_EUNSUPPORTED;
+  const bool wave = rows_fit && !(ctx->msg_at_form == 2 && units_fit);
+  const bool place = units_fit && !(ctx->msg_at_form == 1 && rows_fit);
+  MatArgs M = {};
+  uint64_t *tsize, *glen, *spoff;
+  int32_t *gst;
+  uint32_t *err;
+  if (int rc = carve_reserve(ctx->mat_buf, 1024, [&](Carve &c) {
+        M.send = c.take(nseg);
+        M.base = c.take(nm);
+        M.cap = c.take(nm);
+        tsize = wave ? nullptr : c.take(nm);  // (the wave form's front sizes the tables: msg_front)
+        glen = c.take(nm);
+        spoff = c.take(nseg);
+        gst = reinterpret_cast<int32_t *>(c.take32(nm));
+        err = c.take32(1);  // (a sink: written by the size pass, never cleared, never read)
+      }))
+    return rc;
+  // the form: cpk_encode_batch's rule over the segments as pieces, then the
+  // placed encoder's density rule, then what was enqueued (mat_pick_kernel)
+  if (nseg) {
+    uint32_t samples;
+    if (int rc = gate_arm(ctx, d_swo, nseg, true, d_in, s, samples)) return rc;
+    hipLaunchKernelGGL(e4_gate_kernel, dim3(1), dim3(64), 0, s, ctx->tickets, samples, 0u, d_swo, nseg);
+    hipLaunchKernelGGL(at_gate_kernel, dim3(1), dim3(64), 0, s, ctx->tickets, samples, (uint32_t)ctx->at_form);
   }
-  hipLaunchKernelGGL(cpk::at_prep_kernel, dim3(gg), dim3(tb), 0, s, A, d_grp_piece_off, ustart, pgrp, gfirst);
-  A.pgrp = pgrp;
-  A.gfirst = d_grp_piece_off ? gfirst : ustart;  // (a piece its own group: its first unit)
-  const uint32_t *pick = ctx->tickets + cpk::kTkGate + cpk::kGateSparse;
-  auto launch = [&](auto kernel, int wpe, uint32_t lds, uint32_t form) {
-    hipLaunchKernelGGL(kernel, dim3(sp_grid(ctx, wpe, P)), dim3(cpk::kSpThreads), lds, s, A, P.status, P.epoch,
-                       ctx->tickets + cpk::kTkPlan, P.utab, P.nunits, P.ustate, max_seg_words,
-                       ctx->tickets + cpk::kTkErr, pick, form);
-  };
-  launch(cpk::sp_place_kernel<cpk::SpDense>, cpk::SpDense::kWpe, cpk::SpLay<cpk::SpDense>::kLds, 0u);
-  launch(cpk::sp_place_kernel<cpk::SpSparse>, cpk::SpSparse::kWpe, cpk::SpLay<cpk::SpSparse>::kLds, 1u);
+  const uint32_t *pick = ctx->tickets + kTkGate + kGatePick;
+  hipLaunchKernelGGL(mat_pick_kernel, dim3(1), dim3(64), 0, s, ctx->tickets, wave ? 1u : 0u, place ? 1u : 0u);
+  const unsigned tb = 256, tg = (nm + tb - 1) / tb;
+  MsgPass F = {};
+  if (wave) {
+    // (a segment over max_seg_words is the message's CPK_EINVAL, not the
+    // context's error: the size pass reports it into a word of our own,
+    // which nobody reads; a segment of no message keeps offset and end 0 and
+    // is not emitted)
+    if (int rc = msg_front(ctx, d_in, d_swo, nseg, d_msg_seg_off, nm, max_seg_words, nullptr, s, nseg != 0, F, pick,
+                           err))
+      return rc;
+    M.soff = F.soff;
+    if (nseg && (fill_async(M.send, 0, (uint64_t)nseg * 8, s) != hipSuccess ||
+                 fill_async(M.soff, 0, (uint64_t)nseg * 8, s) != hipSuccess))
+      return CPK_EDEVICE;
+    tsize = F.tsize;
+  } else {
+    hipLaunchKernelGGL(msg_table_size_kernel, dim3(tg), dim3(tb), 0, s, d_swo, d_msg_seg_off, nm, tsize);
+  }
+  M.mseg = d_msg_seg_off;
+  M.tsize = tsize;
+  M.ssize = F.ssize;
+  M.hint = max_seg_words;
+  M.glen = glen;
+  M.gst = gst;
+  M.spoff = spoff;
+  M.pick = pick;
+  const AtArgs U = {(const uint64_t *)d_in, d_swo, nseg, nm, (uint8_t *)d_out, out_cap, d_dst_off, d_dst_cap,
+                    nullptr, nullptr, d_piece_off, d_msg_len, d_status};
+  hipLaunchKernelGGL(mat_slot_kernel, dim3(tg), dim3(tb), 0, s, U, M);
+  if (wave && nseg)
+    e4_emit_launch(ctx, d_in, d_swo, nseg, M.soff, F.ssize, F.stride, pick, F.order, d_out, out_cap, s, M.send);
+  if (place) {
+    // the segments as the placed encoder's pieces, a message's as a group,
+    // behind the table and into what the table left of the slot
+    const AtArgs A = {(const uint64_t *)d_in, d_swo, nseg, nm, (uint8_t *)d_out, out_cap, M.base, M.cap,
+                      nullptr, nullptr, spoff, glen, gst};
+    if (int rc = at_place_launch(ctx, A, d_msg_seg_off, max_seg_words, ub, s)) return rc;
+    hipLaunchKernelGGL(mat_finish_kernel, dim3(tg), dim3(tb), 0, s, U, M);
+  }
   return hip_ok(hipGetLastError());
 }
 

@@ -888,6 +888,7 @@ __global__ void gather8_kernel(Gather8 g, uint32_t k, uint64_t *out) {
 #include "encode_sp3.hip"
 #include "encode_size.hip"
 #include "encode_at.hip"
+#include "encode_msg_at.hip"
 #include "decode_v2.hip"
 #include "stream_split.hip"
 #include "decode_size.hip"

@@ -25,9 +25,10 @@
  * the graph replayed with other data in the same buffers: cpk_encode_batch,
  * cpk_encode_batch_cap, cpk_encode_messages[_cap], cpk_packed_size_batch and
  * cpk_encode_batch_at with max_seg_words != 0, cpk_packed_size_messages,
- * cpk_decode_batch and cpk_unpacked_size_batch (their read-back for n <= 32
- * is skipped while capturing), cpk_decode_batch_at,
- * cpk_unpacked_size_batch_at, cpk_decode_messages_at, cpk_read_message,
+ * cpk_encode_messages_at, cpk_decode_batch and cpk_unpacked_size_batch
+ * (their read-back for n <= 32 is skipped while capturing),
+ * cpk_decode_batch_at, cpk_unpacked_size_batch_at, cpk_decode_messages_at,
+ * cpk_read_message,
  * cpk_generate, cpk_count_mismatch, and cpk_decode_stream below 384 KiB of
  * `avail` (from there on it reads its word total back).  The call must have
  * run once uncaptured on the same context with the same n, counts, bounds and
@@ -35,7 +36,8 @@
  * which a capture does not allow.  Not to be captured: the calls documented
  * to synchronise (cpk_decode_messages, the *_message_stream calls,
  * cpk_ctx_take_error, cpk_ctx_dense_windows, every host form) and
- * max_seg_words == 0.  tests/test_gpu_graph_replay.py replays each of them.
+ * max_seg_words == 0.  tests/test_gpu_graph_replay.py replays each of them
+ * (cpk_encode_messages_at: tests/test_gpu_encode_messages_at_replay.py).
  */
 #ifndef CAPNP_PACKED_H
 #define CAPNP_PACKED_H
@@ -289,6 +291,61 @@ int cpk_encode_batch_at(cpk_ctx ctx, const void *d_in, const uint64_t *d_seg_wor
                         const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
                         uint64_t *d_piece_off, uint64_t *d_grp_len, int32_t *d_status,
                         void *stream);
+
+/* Encode messages to caller-given slots: SerializePacked.write of message m
+ * into the slot d_out + [d_dst_off[m], d_dst_off[m] + d_dst_cap[m]) -- one
+ * packed message per ring-buffer entry or per-peer send buffer, the segment
+ * tables built on the device.  The sender's side of cpk_decode_messages_at.
+ *   Messages: d_in, d_seg_word_off[nseg+1], d_msg_seg_off[nm+1] and
+ *     max_seg_words as for cpk_encode_messages; max_seg_words is required
+ *     (> 0).  Message m's table is built exactly as cpk_encode_messages builds
+ *     it, no table word comes from caller memory, and the message's bytes and
+ *     length are what cpk_encode_messages writes for it: packed(table) ||
+ *     packed(segment 0) || ..., each piece from fresh run state.
+ *   Placement: as cpk_encode_batch_at.  d_dst_off[nm], any byte alignment and
+ *     any order; d_dst_cap[nm], or NULL: every slot runs to out_cap; d_out is
+ *     16-byte aligned, out_cap its bytes; slots must not overlap.
+ *   Written: d_piece_off[nm + nseg], the absolute byte offset in d_out of
+ *     every piece's first packed byte in message order (table, then segments,
+ *     then the next message: the indexing of cpk_encode_messages' d_out_off,
+ *     message m's table is entry d_msg_seg_off[m] + m); d_msg_len[nm], the
+ *     message's exact packed bytes, also when it did not fit; d_status[nm],
+ *     int32, every entry:
+ *       CPK_OK;
+ *       CPK_ENOMEM when d_msg_len[m] > d_dst_cap[m] or the slot passes out_cap
+ *         (no byte outside the message's own slot is stored, the bytes inside
+ *         it are undefined; a table that does not fit is not stored at all);
+ *       CPK_EINVAL when a segment of the message is larger than max_seg_words
+ *         (or 2^31 words and more): the message's length and bytes are
+ *         undefined, nothing outside its slot is stored.
+ *   Bytes of d_out that belong to no message's packed bytes are never written:
+ *     not the gaps between slots, not the unused tail of a slot, not the bytes
+ *     that share a 16-byte line with a message's first or last byte or with
+ *     the seam between a table and its first segment.
+ * Asynchronous on `stream`, no host synchronisation and no read-back at any
+ * nm; cpk_ctx_take_error is not involved, and neither a refused slot nor a
+ * segment over max_seg_words sets the context's error bits.  nm == 0 is
+ * valid.  Missing or misaligned pointers, max_seg_words == 0: CPK_EINVAL with
+ * nothing written.  CPK_EUNSUPPORTED when max_seg_words is so loose that nseg
+ * segments of it pass both forms' workspace bounds (4 GiB of the size pass's
+ * rows, 24 bytes per 64 words, and 2^25 chunks of 8192 words).
+ * Round trip: d_dst_off and d_msg_len are cpk_decode_messages_at's d_src_off
+ * and d_src_len; the lengths are the per-message differences of what
+ * cpk_packed_size_messages reports.
+ * Two forms, both enqueued, one picked on the device by the rule
+ * cpk_encode_batch applies to the same segments as pieces: the two passes (a
+ * wave per segment, each segment emitted against its own slot's end; nothing
+ * of a refused message is stored), or, for like-sized segments of 4 Ki words
+ * and more or one dominant segment, the placed single pass of
+ * cpk_encode_batch_at over the segments behind each table (dense or sparse
+ * as there, CPK_AT_FORM).  CPK_MSG_AT_FORM=wave|place, read at context
+ * creation, forces a form.  There is no host form. */
+int cpk_encode_messages_at(cpk_ctx ctx, const void *d_in, const uint64_t *d_seg_word_off, uint32_t nseg,
+                           const uint64_t *d_msg_seg_off, uint32_t nm, uint64_t max_seg_words,
+                           void *d_out, uint64_t out_cap,
+                           const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
+                           uint64_t *d_piece_off, uint64_t *d_msg_len, int32_t *d_status,
+                           void *stream);
 
 /* Batch decode of n pieces, device-resident (replaces n calls of
  * PackedInputStream.read, PackedInputStream.java:35-140).
